@@ -5,6 +5,10 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`.  For N > 1 t
 torch.distributed.run (one rank per GPU); started WITHOUT that environment, `--gpus N` re-executes itself under
 torch.distributed.run and fails loudly when fewer than N GPUs are visible.  One JSON line on stdout (rank 0).
 
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `roofline` of the timed
+steps).  `--full` adds everything else below: the extra rates, `value_tables_only`, `parity`, `cpu_baseline`, `vgg16`.
+`--dump-outputs DIR` writes what the last timed step returned (soft-max outputs, top-5) as float32 .npy files.
+
 A step = one pass of the hot path (23 AlexNet layers: LUT build + indexed accumulation for conv/FC, glue layers,
 top-5) over one batch of synthetic images already resident in HBM.
   N = 1   the batch is BASELINE.json configs[1]: 1000 images on one GPU.
@@ -291,6 +295,26 @@ def timed(torch, dev, fn, steps):
     return time.perf_counter() - t0
 
 
+DUMP_LIMIT = 64 << 20                       # bytes --dump-outputs may write
+
+
+def dump_outputs(d, prob, top5, suffix):
+    """--dump-outputs: what the last timed step returned to its caller for this rank's images — soft-max outputs [n, classes]
+    and top-5 class indices [n, 5] — as float32 d/prob<suffix>.npy and d/top5<suffix>.npy (1000 AlexNet images: 4 MB).  Beyond
+    DUMP_LIMIT a fixed seeded sample of rows is written instead, their indices in d/rows<suffix>.npy."""
+    p = prob.cpu().numpy().astype(np.float32)
+    t = top5.cpu().numpy().view(np.uint16).astype(np.float32)
+    os.makedirs(d, exist_ok=True)
+    n = p.shape[0]
+    keep = min(n, DUMP_LIMIT // (4 * (p.shape[1] + t.shape[1]) + 8))
+    if keep < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        p, t = p[rows], t[rows]
+        np.save(os.path.join(d, "rows%s.npy" % suffix), rows.astype(np.float64))
+    np.save(os.path.join(d, "prob%s.npy" % suffix), p)
+    np.save(os.path.join(d, "top5%s.npy" % suffix), t)
+
+
 def group_capi_child(args):
     """Child process of the N = 1 bench: one batch through qcnn_group_forward over every visible device (see the call site)."""
     import torch
@@ -357,9 +381,17 @@ def main():
     ap.add_argument("--vgg-batch", type=int, default=1000, help="images of the VGG-16 run (BASELINE configs[3]; SURVEY.md §8d: 1000)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = one --batch sharded over the GPUs (BASELINE configs[2]); weak = --batch per GPU")
-    ap.add_argument("--cpu-sample", type=int, default=100, help="images for the CPU baseline (0 = skip)")
-    ap.add_argument("--parity-images", type=int, default=8, help="images checked against the CPU reference (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="0 = only the headline measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the extra rates (two streams, tables only, fp16 tables, small "
+                         "batches, shards, PCIe-inclusive, device group, reference Main.cc, VGG-16), the parity checks against the CPU "
+                         "reference and the CPU baseline.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller (soft-max outputs, top-5 class "
+                         "indices) as float32 DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="images for the CPU baseline (0 = skip; default: 100 with --full, else 0)")
+    ap.add_argument("--parity-images", type=int, default=None,
+                    help="images checked against the CPU reference (0 = skip; default: 8 with --full, else 0)")
+    ap.add_argument("--extras", type=int, default=None, help="0 = only the headline measurement (default: 1 with --full, else 0)")
     ap.add_argument("--sym8", type=int, default=-1,
                     help="QCNN_OPT_SYM8 (eight-wave symmetric workgroups): -1 = library default (1 = planner), 0 off, 2 forced tile form, 3 forced sliding form")
     ap.add_argument("--dry-run-shared-gpu", type=int, default=0,
@@ -378,6 +410,14 @@ def main():
                          "library default is 2).  1 keeps one launch per layer, so that the per-kernel HIP-event "
                          "durations behind `roofline` are those of kernels that own the whole GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.extras is None:
+        args.extras = 1 if args.full else 0
+    if args.parity_images is None:
+        args.parity_images = 8 if args.full else 0
+    if args.cpu_sample is None:
+        args.cpu_sample = 100 if args.full else 0
 
     if args.group_capi_child:
         return group_capi_child(args)
@@ -552,6 +592,8 @@ def main():
 
     dt = measure(step, args.steps, args.warmup)
     snap = snapshot()
+    if args.dump_outputs and n_local > 0:
+        dump_outputs(args.dump_outputs, prob[lo:hi], top5[lo:hi], "" if world == 1 else ".rank%d" % rank)
     decoded = snap["decoded"]
     ok = bool(torch.isfinite(prob[lo:hi]).all().item())
     images_per_step = B if (strong or world == 1) else B * world
@@ -1012,7 +1054,7 @@ def main():
                 out.update(alg_north_star_value=out["value"], alg_north_star_ms_per_step=out["ms_per_step"], alg_north_star_roofline_frac=roof.get("frac"),
                            alg_north_star_note="`value` itself: no layer of this run was decoded")
             else:
-                out["alg_north_star_note"] = "not measured in this run (--extras 0 or N > 1): see value_tables_only of the N = 1 line"
+                out["alg_north_star_note"] = "not measured in this run (no --full, --extras 0 or N > 1): see value_tables_only of the N = 1 --full line"
         out.update(extras)
         if value_weak is not None:
             out["value_weak"] = round(value_weak, 2)

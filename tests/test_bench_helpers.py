@@ -75,3 +75,24 @@ def test_layer_report_for_every_kernel_family():
                     assert r["rebuild_factor"] < r8["rebuild_factor"], (model, i, r["rebuild_factor"], r8["rebuild_factor"])
                 for key in ("stages_per_panel", "rebuild_factor", "lookups_per_stage", "stage_cycles", "lds_frac"):
                     assert np.isfinite(r[key]) and r[key] > 0, (model, i, kw, key, r)
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the soft-max rows and top-5 lists as float32 .npy files; above the size limit a fixed seeded
+    sample of rows, the same one every run, with its row indices beside it."""
+    import torch
+    rng = np.random.default_rng(5)
+    prob = torch.from_numpy(rng.random((40, 1000), dtype=np.float32))
+    top5 = torch.from_numpy(rng.integers(0, 1000, (40, 5)).astype(np.int16))
+    bench.dump_outputs(str(tmp_path / "all"), prob, top5, "")
+    p, t = np.load(tmp_path / "all" / "prob.npy"), np.load(tmp_path / "all" / "top5.npy")
+    assert p.dtype == np.float32 and t.dtype == np.float32 and not os.path.exists(tmp_path / "all" / "rows.npy")
+    assert np.array_equal(p, prob.numpy()) and np.array_equal(t, top5.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 16 * (4 * 1005 + 8))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), prob, top5, ".rank1")
+    rows = np.load(tmp_path / "s1" / "rows.rank1.npy").astype(np.int64)
+    assert len(rows) == 16 and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.rank1.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "prob.rank1.npy"), prob.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "top5.rank1.npy"), top5.numpy()[rows].astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= bench.DUMP_LIMIT + 3 * 128

@@ -105,7 +105,7 @@ def test_bench_multi_rank_code_path_dry_run():
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-shared-gpu", "1", "--steps", "2",
-                        "--warmup", "1", "--extras", "0", "--cpu-sample", "0", "--parity-images", "4"],
+                        "--warmup", "1", "--full", "--extras", "0", "--cpu-sample", "0", "--parity-images", "4"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
