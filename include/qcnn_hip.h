@@ -28,6 +28,8 @@
  *   qcnn_forward_u8             BmpImgIO::RmMeanImg + CropImg in front     src/BmpImgIO.cc:180-224
  *   qcnn_model_set_layer_dense  CaffePara::LoadLayerPara(false, ..) result src/CaffePara.cc:290-302
  *   / _set_layer_weights        -> CalcFeatMap_ConvPrec / _FCntPrec        src/CaffeEva.cc:681-758, 932-966
+ *   qcnn_quantize_layer         produces what CaffePara::LoadLayerPara reads src/CaffePara.cc:262-288
+ *                               (sub-codebooks + assignments) from the dense weights of :290-302
  *   qcnn_run_layer              CaffeEva::CalcFeatMap on one layer         src/CaffeEva.cc:625-670
  *   qcnn_get_layer_output       featMapLst[l] read-back (parity dumps)     include/CaffeEva.h:109
  *   qcnn_get_layer_ms           swIndvLayerLst / DispElpsTime              src/CaffeEva.cc:297-326
@@ -182,6 +184,28 @@ int qcnn_model_set_layer_shape(QcnnCtx* ctx, int layer, int M, int K, int Cs);
  * (convKnl.NN.bin), FC weights [Ct][D] (fcntWei.NN.bin).  Dense and quantised layers may be mixed in one model. */
 int qcnn_model_set_layer_dense(QcnnCtx* ctx, int layer);
 int qcnn_model_set_layer_weights(QcnnCtx* ctx, int layer, const float* bias, const float* weights_file);
+/* Quantise one dense conv / FC layer into the parameters qcnn_model_set_layer_params takes: product-quantisation k-means
+ * (Lloyd's algorithm), deterministic to the bit (DESIGN.md "Quantising dense weights").  The reference ships only the result
+ * of this step; the layout is the one its approximate path reads: sub-codebooks ctrdLst [M][K][Cs] and 0-based assignments
+ * asmtLst [Ct][kh][kw][M] (CaffePara::LoadLayerPara src/CaffePara.cc:262-288, consumed by GetInPdMat src/CaffeEva.cc:1261-1296).
+ *   weights    the dense layer in the precise path's file layout (src/CaffePara.cc:290-302): conv kernels [Ct][Cin][kh][kw]
+ *              (convKnl, Cin = channels per group) or FC weights [Ct][D] with kh = kw = 1, Cin = D (fcntWei)
+ *   points     sub-space m holds N = Ct*kh*kw points, point n = (ct*kh + y)*kw + x being W[ct][m*Cs + j][y][x] for
+ *              j < CsEff(m) = min(Cin - m*Cs, Cs) (the dims rule of src/CaffeEva.cc:1277)
+ *   distance   fp32, d = 0; for j < CsEff: t = p_j - c_j; d = d + t*t (one rounding per operation, no FMA); nearest code
+ *              word: the lowest k of the minimum
+ *   update     c_k[j] = (float)(fp64 sum of the members' p_j in ascending n / members); a code word without members keeps its value
+ *   seeding    ctrd_init ([M][K][Cs]) when given, else farthest-first: c_0 = point 0, then the point farthest from its nearest
+ *              chosen code word (ties: lowest n)
+ *   loop       a = assign(C); up to max_iter times: C = update(C, a), a' = assign(C), stop when a' == a in every sub-space
+ * Outputs: ctrd_out [M][K][Cs] (dims >= CsEff written as 0), asmt_out 0-based [Ct][kh][kw][M] (FC: [Ct][M]); sse2 (may be
+ * NULL) = fp64 sums of the minimum distances before the first and after the last step; iters2 (may be NULL) = update steps
+ * taken, sub-spaces still changing when max_iter ran out.  Needs 1 <= Cs <= 16, 2 <= K <= 256, (M-1)*Cs < Cin <= M*Cs,
+ * max_iter >= 0 and finite weights.  Blocking; device scratch is allocated per call and freed before return; works with or
+ * without a model loaded and changes nothing of it. */
+int qcnn_quantize_layer(QcnnCtx* ctx, int Ct, int Cin, int kh, int kw, int M, int K, int Cs, const float* weights_host,
+                        const float* ctrd_init_host, int max_iter, float* ctrd_out_host, uint8_t* asmt_out_host, double* sse2,
+                        int* iters2);
 /* Size of the packed parameter arena (biases, permuted codebooks, permuted assignments). */
 int qcnn_model_arena_bytes(QcnnCtx* ctx, size_t* bytes);
 /* Plan buffers for up to max_batch images.  dev_arena: caller-owned device memory of

@@ -7,6 +7,7 @@ The directory name carries a hyphen (it mirrors the reference repo's name), so i
 
 Sub-modules: ``fileio`` (.bin/.cbn formats), ``topology`` (layer tables), ``synth`` (seeded parameter
 sets), ``build`` (hipcc / g++ recipes), ``capi`` (ctypes binding of include/qcnn_hip.h),
-``engine`` (CaffeEva-shaped Python driver used by bench.py and the tests).
+``engine`` (CaffeEva-shaped Python driver used by bench.py and the tests), ``quantize`` (dense weights -> Q-CNN
+parameters on the GPU, and back).
 """
-__all__ = ["fileio", "topology", "synth", "build", "capi", "engine"]
+__all__ = ["fileio", "topology", "synth", "build", "capi", "engine", "quantize"]

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <string>
 #include <vector>
@@ -1076,6 +1077,114 @@ int qcnn_model_set_layer_weights(QcnnCtx* c, int layer, const float* bias, const
   HIP_TRY(c, hipMemcpyAsync(c->arena + s.offDense, wt.data(), sizeof(float) * wt.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   s.loaded = true;
+  return 0;
+}
+
+namespace {
+// device scratch of one qcnn_quantize_layer call: freed on every return path
+struct PqScratch {
+  std::vector<void*> bufs;
+  hipError_t alloc(void** p, size_t bytes) {
+    *p = nullptr;
+    hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 1));
+    if (e == hipSuccess) bufs.push_back(*p);
+    return e;
+  }
+  ~PqScratch() { for (void* v : bufs) (void)hipFree(v); }
+};
+}  // namespace
+
+int qcnn_quantize_layer(QcnnCtx* c, int Ct, int Cin, int kh, int kw, int M, int K, int Cs, const float* weights, const float* ctrd_init,
+                        int max_iter, float* ctrd_out, uint8_t* asmt_out, double* sse2, int* iters2) {
+  if (!c) return fail(nullptr, "qcnn_quantize_layer: ctx == NULL");
+  if (Ct <= 0 || Cin <= 0 || kh <= 0 || kw <= 0) return fail(c, "qcnn_quantize_layer: bad layer shape Ct=%d Cin=%d kh=%d kw=%d", Ct, Cin, kh, kw);
+  if (Cs < 1 || Cs > QCNN_PQ_MAX_CS) return fail(c, "qcnn_quantize_layer: Cs=%d outside [1, %d]", Cs, QCNN_PQ_MAX_CS);
+  if (K < 2 || K > QCNN_PQ_MAX_K) return fail(c, "qcnn_quantize_layer: K=%d outside [2, %d]", K, QCNN_PQ_MAX_K);
+  if (M < 1 || (long long)M * Cs < Cin) return fail(c, "qcnn_quantize_layer: M*Cs = %lld does not cover Cin = %d", (long long)M * Cs, Cin);
+  if ((long long)(M - 1) * Cs >= Cin) return fail(c, "qcnn_quantize_layer: sub-space %d starts beyond Cin = %d (M*Cs must be < Cin + Cs)", M - 1, Cin);
+  if (max_iter < 0) return fail(c, "qcnn_quantize_layer: max_iter=%d < 0", max_iter);
+  if (!weights || !ctrd_out || !asmt_out) return fail(c, "qcnn_quantize_layer: weights, ctrd_out and asmt_out must not be NULL");
+  const int taps = kh * kw;
+  const long long Nll = (long long)Ct * taps;
+  if (Nll * M >= (1LL << 31) || (Nll + 127) / 128 >= 65536) return fail(c, "qcnn_quantize_layer: %lld points x %d sub-spaces is too large", Nll, M);
+  const int N = (int)Nll;
+  const size_t wElems = (size_t)Nll * Cin;
+  for (size_t i = 0; i < wElems; ++i)
+    if (!std::isfinite(weights[i])) return fail(c, "qcnn_quantize_layer: weight %zu is not finite", i);
+  const size_t cbElems = (size_t)M * K * Cs;
+  if (ctrd_init)
+    for (size_t i = 0; i < cbElems; ++i)
+      if ((int)(i / ((size_t)K * Cs)) * Cs + (int)(i % Cs) < Cin && !std::isfinite(ctrd_init[i]))
+        return fail(c, "qcnn_quantize_layer: initial code book entry %zu is not finite", i);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t MN = (size_t)M * N;
+  PqScratch sc;
+  float *dW = nullptr, *pts = nullptr, *ctrd = nullptr, *dmin = nullptr;
+  uint8_t* asmt = nullptr;
+  int* chg = nullptr;
+  double* partial = nullptr;
+  const int nPart = qk_pq_finalize_blocks(MN);
+  HIP_TRY(c, sc.alloc((void**)&pts, MN * Cs * sizeof(float)));
+  HIP_TRY(c, sc.alloc((void**)&ctrd, cbElems * sizeof(float)));
+  HIP_TRY(c, sc.alloc((void**)&dmin, MN * sizeof(float)));
+  HIP_TRY(c, sc.alloc((void**)&asmt, MN));
+  HIP_TRY(c, sc.alloc((void**)&chg, 2 * sizeof(int) * M));            // two changed-flag sets: the last step's (= this step's active set) and this step's
+  HIP_TRY(c, sc.alloc((void**)&partial, nPart * sizeof(double)));
+  {
+    PqScratch wsc;                                        // the dense weights live only until they are gathered into points
+    HIP_TRY(c, wsc.alloc((void**)&dW, wElems * sizeof(float)));
+    HIP_TRY(c, hipMemcpyAsync(dW, weights, wElems * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, qk_pq_gather(dW, pts, N, Cin, taps, M, Cs, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+  }
+  if (ctrd_init) {
+    HIP_TRY(c, hipMemcpyAsync(ctrd, ctrd_init, cbElems * sizeof(float), hipMemcpyHostToDevice, st));
+  } else {
+    HIP_TRY(c, qk_pq_seed(pts, ctrd, dmin, M, N, K, Cs, st));
+  }
+  std::vector<double> part(nPart);
+  auto sse = [&](double* out) -> int {
+    HIP_TRY(c, qk_pq_finalize(dmin, MN, ctrd, M, K, Cs, Cin, partial, st));
+    HIP_TRY(c, hipMemcpyAsync(part.data(), partial, nPart * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    double s = 0.0;
+    for (double v : part) s += v;
+    *out = s;
+    return 0;
+  };
+  double sseInit = 0.0, sseFinal = 0.0;
+  HIP_TRY(c, qk_pq_assign(pts, ctrd, asmt, dmin, nullptr, nullptr, M, N, K, Cs, Cin, 1, st));
+  if (sse(&sseInit)) return 1;
+  // Lloyd steps: update, then re-assign, on the sub-spaces whose assignments changed in the previous step (all at first).  A
+  // sub-space whose assignments did not change is a fixed point: leaving it alone gives the bits running it would give.
+  std::vector<int> flags(M);
+  int steps = 0, changing = 0;
+  int* active = nullptr;
+  int* cur = chg;
+  for (int it = 0; it < max_iter; ++it) {
+    HIP_TRY(c, qk_pq_update(pts, ctrd, asmt, active, M, N, K, Cs, Cin, st));
+    HIP_TRY(c, hipMemsetAsync(cur, 0, sizeof(int) * M, st));
+    HIP_TRY(c, qk_pq_assign(pts, ctrd, asmt, dmin, cur, active, M, N, K, Cs, Cin, 0, st));
+    HIP_TRY(c, hipMemcpyAsync(flags.data(), cur, sizeof(int) * M, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    ++steps;
+    changing = 0;
+    for (int v : flags) changing += v != 0;
+    if (!changing) break;
+    active = cur;
+    cur = (cur == chg) ? chg + M : chg;
+  }
+  if (sse(&sseFinal)) return 1;
+  HIP_TRY(c, hipMemcpyAsync(ctrd_out, ctrd, cbElems * sizeof(float), hipMemcpyDeviceToHost, st));
+  // device [M][N] -> file order [Ct][kh][kw][M] = [N][M]
+  std::vector<uint8_t> a(MN);
+  HIP_TRY(c, hipMemcpyAsync(a.data(), asmt, MN, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < N; ++n) asmt_out[(size_t)n * M + m] = a[(size_t)m * N + n];
+  if (sse2) { sse2[0] = sseInit; sse2[1] = sseFinal; }
+  if (iters2) { iters2[0] = steps; iters2[1] = changing; }
   return 0;
 }
 

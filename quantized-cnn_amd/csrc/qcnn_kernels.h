@@ -421,4 +421,17 @@ hipError_t qk_pack_rows(const float* in, float* dst, int n, int E, hipStream_t s
 // panels [E][128] -> [n][E]
 hipError_t qk_unpack_rows(const float* src, float* out, int n, int E, hipStream_t st);
 
+// Product-quantisation k-means of one dense layer (qcnn_quantize.hip, behind qcnn_quantize_layer).  pts [M][N][Cs] (dims >= CsEff
+// zero), ctrd [M][K][Cs], asmt / dmin [M][N]; chg / active [M] (active == NULL: every sub-space); first = 1: no changed-flags.
+#define QCNN_PQ_MAX_K 256
+#define QCNN_PQ_MAX_CS 16
+hipError_t qk_pq_gather(const float* w, float* pts, int N, int Cin, int taps, int M, int Cs, hipStream_t st);
+hipError_t qk_pq_seed(const float* pts, float* ctrd, float* dmin, int M, int N, int K, int Cs, hipStream_t st);
+hipError_t qk_pq_assign(const float* pts, const float* ctrd, uint8_t* asmt, float* dmin, int* chg, const int* active, int M, int N,
+                        int K, int Cs, int Cin, int first, hipStream_t st);
+hipError_t qk_pq_update(const float* pts, float* ctrd, const uint8_t* asmt, const int* active, int M, int N, int K, int Cs, int Cin,
+                        hipStream_t st);
+int qk_pq_finalize_blocks(size_t total);     // doubles of the partial-sum buffer qk_pq_finalize writes
+hipError_t qk_pq_finalize(const float* dmin, size_t total, float* ctrd, int M, int K, int Cs, int Cin, double* partial, hipStream_t st);
+
 #endif  // QCNN_KERNELS_H_

@@ -19,6 +19,9 @@ class QcnnError(RuntimeError):
     pass
 
 
+DEFAULT_MAX_ITER = 30     # Lloyd steps of quantize_layer / quantize.quantize_model unless the caller says otherwise
+
+
 class QcnnEngine:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load()
@@ -122,6 +125,34 @@ class QcnnEngine:
             bias = np.ascontiguousarray(p["bias"], np.float32)
             w = np.ascontiguousarray(p["weights"], np.float32)
             self._chk(self.lib.qcnn_model_set_layer_weights(self.h, i, bias.ctypes.data, w.ctypes.data))
+
+    def quantize_layer(self, weights, M, K, Cs, ctrd_init=None, max_iter=DEFAULT_MAX_ITER):
+        """Product-quantisation k-means of one dense layer on this context's GPU (qcnn_quantize_layer).  weights: conv kernels
+        [Ct][Cin][kh][kw] (convKnl layout) or FC weights [Ct][D] (fcntWei).  Returns (ctrd [M][K][Cs] float32, asmt uint8 0-based
+        in file order [Ct][kh][kw][M] / [Ct][M], stats dict(sse_init, sse, iters, unconverged)).  Needs no loaded model and leaves
+        a loaded one untouched."""
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.ndim == 4:
+            ct, cin, kh, kw = w.shape
+            ashape = (ct, kh, kw, M)
+        elif w.ndim == 2:
+            (ct, cin), kh, kw = w.shape, 1, 1
+            ashape = (ct, M)
+        else:
+            raise QcnnError("weights must be [Ct][Cin][kh][kw] or [Ct][D], got shape %r" % (w.shape,))
+        init = None
+        if ctrd_init is not None:
+            init = np.ascontiguousarray(ctrd_init, np.float32)
+            if init.shape != (M, K, Cs):
+                raise QcnnError("ctrd_init must be [M][K][Cs] = %r, got %r" % ((M, K, Cs), init.shape))
+        ctrd = np.empty((max(M, 0), max(K, 0), max(Cs, 0)), np.float32)
+        asmt = np.empty(tuple(max(x, 0) for x in ashape), np.uint8)
+        sse = (C.c_double * 2)()
+        it = (C.c_int * 2)()
+        self._chk(self.lib.qcnn_quantize_layer(self.h, ct, cin, kh, kw, M, K, Cs, w.ctypes.data,
+                                               init.ctypes.data if init is not None else None, max_iter,
+                                               ctrd.ctypes.data, asmt.ctypes.data, sse, it))
+        return ctrd, asmt, dict(sse_init=float(sse[0]), sse=float(sse[1]), iters=int(it[0]), unconverged=int(it[1]))
 
     def fm_dims(self, l):
         d = (C.c_int * 3)()
