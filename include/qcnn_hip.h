@@ -146,6 +146,11 @@ enum {
                               per segment); 2 = the tile form whenever eligible, 3 = the sliding form whenever eligible (tests); 0 = never.
                               Same table entries in the same order: bit-identical to the other f32 table kernels.
                               qcnn_get_layer_split reports (-9, 1) / (-10, segments per column) */
+  QCNN_OPT_DEC_BF16SPLIT = 14, /* 1 (default): a first layer read in place (QCNN_OPT_DIRECT_DEC) whose code words fit the LDS as two
+                              bf16 pieces (Cin knl^2 rounded up to 32, times the channels, times 4 bytes <= 158 KB) computes its products
+                              on the bf16 matrix pipe at fp32 accuracy: activations and code words split exactly into three bf16 pieces
+                              each, the six cross terms down to order 2^-16 summed in fp32 (k_conv_dec_nchw_split).  Not bit-identical
+                              to 0 = the f32 matrix instructions (k_conv_dec_nchw); batch-size invariant like it. */
   QCNN_OPT_HOST_CHUNK = 6, /* panels per chunk (default 2) of a qcnn_forward_host batch of at least two chunks: every chunk is
                               uploaded on a copy stream and its layers start when it has arrived, so the upload of chunk
                               k + 1 runs under the layers of chunk k; all chunks fill the same whole-batch feature maps.

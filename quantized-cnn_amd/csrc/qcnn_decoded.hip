@@ -514,6 +514,269 @@ __global__ void k_decode_weights_nchw(const uint8_t* __restrict__ rows, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// k_conv_dec_nchw_split (QCNN_OPT_DEC_BF16SPLIT, default): the same layer at fp32 accuracy on the BF16 matrix pipe.  The
+// f32 kernel above is bound by v_mfma_f32_16x16x4_f32 (32 cycles per 4 k: 1.42 of its 1.85 ms); gfx950 has no xf32, and its
+// bf16 rate is 16x the f32 one.  Every fp32 value splits EXACTLY into three bf16 pieces (round to nearest, remainder in
+// fp32: 8 + 8 + 8 significant bits), x = x1 + x2 + x3, w = w1 + w2 + w3, and the six cross terms down to order 2^-16,
+//     x3 w1, x2 w2, x1 w3, x2 w1, x1 w2, x1 w1      (in that order: small terms first),
+// go to v_mfma_f32_16x16x32_bf16 — each bf16 x bf16 product is exact in fp32, the accumulator is fp32 — while the dropped
+// x2 w3, x3 w2, x3 w3 are of order 2^-24, one fp32 rounding.  Six 16-cycle MFMAs per 32 k: 3 cycles per k against 8.
+// Layout: a lane (li, kg) of a 16x16x32 product holds row li (image li & 7, position li >> 3: the tile of the f32 kernel)
+// and k = 8 kg .. 8 kg + 7 of the step; k is flat over the window as above, padded to a multiple of 32 (the offset table
+// repeats the window's last element, the code words there are zero).  A step: 8 dword loads per image tile (same loads per
+// k as the f32 kernel), split once in registers and shared by the six channel tiles (36 MFMAs per fragment).  Code words:
+// the decoder writes the pieces once per upload; w1 and w2 stay in LDS (Kb x Ct x 4 bytes: 144 KB for AlexNet conv1 — all
+// three planes would be 216 KB), w3 (74 KB) streams from L2 through the buffer loads, one dwordx4 per channel tile and step.
+// Operand loads are inline assembly with counted waits (see the f32 kernel): step s splits its raw values, issues step
+// s + 1's loads into the same registers, then runs its channel tiles, each followed by the w3 load of step s + 1.  The
+// sum per output — bias, then per step the six terms in fixed order — depends on nothing but the output, as before.
+// ------------------------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// x = x1 + x2 + x3 exactly (finite x; v_cvt_pk_bf16_f32 rounds to nearest even)
+__device__ __forceinline__ void split_bf16x8(const f32x4 (&x)[2], bf16x8& h1, bf16x8& h2, bf16x8& h3) {
+  u32x4 p1, p2, p3;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float x0 = x[q >> 1][2 * (q & 1)], x1 = x[q >> 1][2 * (q & 1) + 1];
+    const unsigned a = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
+    const float r0 = x0 - __builtin_bit_cast(float, a << 16), r1 = x1 - __builtin_bit_cast(float, a & 0xffff0000u);
+    const unsigned b = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
+    const float s0 = r0 - __builtin_bit_cast(float, b << 16), s1 = r1 - __builtin_bit_cast(float, b & 0xffff0000u);
+    p1[q] = a; p2[q] = b;
+    p3[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
+  }
+  h1 = __builtin_bit_cast(bf16x8, p1); h2 = __builtin_bit_cast(bf16x8, p2); h3 = __builtin_bit_cast(bf16x8, p3);
+}
+
+template <int N>
+__device__ __forceinline__ void split_wait(f32x4 (&x)[4][2]) {
+  asm volatile("s_waitcnt vmcnt(%8)" : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]),
+               "+v"(x[3][0]), "+v"(x[3][1]) : "n"(N));
+}
+template <int N>
+__device__ __forceinline__ void split_wait(u32x4& w) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w) : "n"(N)); }
+
+template <int CT, int IT>
+__global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecParams p) {
+  static_assert(IT == 4 && CT == 6, "a product tile is 2 positions x 8 images, an item two pairs of positions x two image halves x 96 channels");
+  extern __shared__ __attribute__((aligned(16))) float ldsW[];          // [steps][S / 16][piece 2][64 lanes][8 bf16], then int [Kp + 32]
+  const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
+  const int P = p.Ho * p.Wo;
+  const int steps = p.Kp >> 5;                                          // Kp: Cin knl^2 padded to a multiple of 32
+  const int CTs = p.S >> 4;                                             // channel tiles of the layer
+  const uint32_t imgBytes = (uint32_t)p.Cin * p.H * p.W * 4u, planeBytes = (uint32_t)p.H * p.W * 4u, rowBytes = (uint32_t)p.W * 4u;
+  int* ldsOff = reinterpret_cast<int*>(ldsW + (size_t)p.Kp * p.S);
+  {
+    const int wq = (p.Kp * p.S) >> 2;                                   // w1, w2: 4 bytes per code word
+    const f32x4* __restrict__ wsrc = reinterpret_cast<const f32x4*>(p.wdec);
+    f32x4* ldsW4 = reinterpret_cast<f32x4*>(ldsW);
+    for (int i = threadIdx.x; i < wq; i += 64 * NCHW_WAVES) ldsW4[i] = wsrc[i];
+    for (int i = threadIdx.x; i < p.Kp + 32; i += 64 * NCHW_WAVES) {
+      const int k = min(i, p.Kr - 1);
+      const int kw = k % p.knl, kh = (k / p.knl) % p.knl, c = k / (p.knl * p.knl);
+      ldsOff[i] = (int)((uint32_t)c * planeBytes + (uint32_t)kh * rowBytes + (uint32_t)kw * 4u);
+    }
+  }
+  __syncthreads();
+  const int tiles = (p.live + 15) / 16;
+  const int chunks = p.Ct / (16 * CT);
+  const int WoG = (p.Wo + IT - 1) / IT, PG = p.Ho * WoG;
+  const int nItems = p.panels * PG * tiles * chunks;
+  const unsigned long long total = (unsigned long long)p.nImages * imgBytes;
+  typedef int i32x4_t __attribute__((ext_vector_type(4)));
+  const unsigned long long srcA = reinterpret_cast<unsigned long long>(p.src);
+  const i32x4_t rsrc4 = {(int)(unsigned)srcA, (int)((unsigned)(srcA >> 32) & 0xffffu),
+                         (int)(total < 0xffffffffull ? (unsigned)total : 0xffffffffu), 0x00020000};
+  // w3: [steps][S / 16][64 lanes][8 bf16] behind w1 / w2; the step in the VECTOR offset, so that the range check turns the
+  // last step's pre-load of "step `steps`" into zeros
+  const unsigned long long w3A = reinterpret_cast<unsigned long long>(p.wdec) + (size_t)p.Kp * p.S * 4;
+  const uint32_t w3Bytes = (uint32_t)p.Kp * p.S * 2u, w3Step = (uint32_t)p.S * 64u;
+  const i32x4_t rsrcW = {(int)(unsigned)w3A, (int)((unsigned)(w3A >> 32) & 0xffffu), (int)w3Bytes, 0x00020000};
+  const int xcd = blockIdx.x & 7, nX = gridDim.x < 8 ? gridDim.x : 8;
+  const int wgX = (gridDim.x - xcd + 7) >> 3;
+  const int itemBeg = (int)((long long)nItems * xcd / nX), itemEnd = (int)((long long)nItems * (xcd + 1) / nX);
+  const bool sparse = itemEnd - itemBeg <= wgX * NCHW_WAVES;
+  for (int item = itemBeg + (sparse ? wave * wgX + (int)(blockIdx.x >> 3) : (int)(blockIdx.x >> 3) * NCHW_WAVES + wave); item < itemEnd;
+       item += wgX * NCHW_WAVES) {
+    int laneI = lane;
+    asm volatile("" : "+v"(laneI));
+    const int li = laneI & 15, kg = laneI >> 4;
+    const int it = item % tiles, cc = (item / tiles) % chunks, pg = (item / (tiles * chunks)) % PG, panel = item / (chunks * tiles * PG);
+    const int orow = pg / WoG, ocol = (pg % WoG) * IT;
+    const int r0 = orow * p.stride, c0 = ocol * p.stride;
+    const uint32_t img0 = (uint32_t)(p.panel0 + panel) * PANEL + (uint32_t)it * 16u;
+    const bool edge = img0 + 16u >= (uint32_t)p.nImages;                // every address clamped inside the batch: see k_conv_dec_nchw
+    const int laneOff = (int)((uint32_t)(li & 7) * imgBytes + (uint32_t)((li >> 3) * p.stride) * 4u);
+    const uint32_t base0 = img0 * imgBytes + (uint32_t)(r0 * p.W + c0) * 4u;
+   auto body = [&](auto edgeTag) {
+    constexpr bool EDGE = decltype(edgeTag)::value;
+    int laneOffE[IT];
+    uint32_t baseS[IT];
+#pragma unroll
+    for (int ti = 0; ti < IT; ++ti) {
+      laneOffE[ti] = laneOff;
+      baseS[ti] = base0 + (uint32_t)(ti & 1) * 8u * imgBytes + (uint32_t)((ti >> 1) * 2 * p.stride) * 4u;
+    }
+    if constexpr (EDGE) {
+      const uint32_t lastImg = (uint32_t)p.nImages - 1u, lastPos = (uint32_t)p.Wo - 1u;
+#pragma unroll
+      for (int ti = 0; ti < IT; ++ti) {
+        const uint32_t imgS = min(img0 + 8u * (uint32_t)(ti & 1), lastImg), imgL = min(img0 + 8u * (uint32_t)(ti & 1) + (uint32_t)(li & 7), lastImg);
+        const uint32_t posS = min((uint32_t)ocol + 2u * (uint32_t)(ti >> 1), lastPos), posL = min((uint32_t)ocol + 2u * (uint32_t)(ti >> 1) + (uint32_t)(li >> 3), lastPos);
+        laneOffE[ti] = (int)((imgL - imgS) * imgBytes + (posL - posS) * (uint32_t)p.stride * 4u);
+        baseS[ti] = imgS * imgBytes + ((uint32_t)(r0 * p.W) + posS * (uint32_t)p.stride) * 4u;
+      }
+    }
+    const int* __restrict__ offT = ldsOff + 8 * kg;
+    f32x4 xr[IT][2];                                                    // raw operands of the next step
+    // the 8 x IT operand loads of step s (lane: k = 32 s + 8 kg + j)
+    auto issue_x = [&, rsrc4](int s) {
+      const i32x4_t o0 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s), o1 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s + 4);
+      const int ot[8] = {o0[0], o0[1], o0[2], o0[3], o1[0], o1[1], o1[2], o1[3]};
+#pragma unroll
+      for (int ti = 0; ti < IT; ++ti)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float v;
+          if (NCHW_VAR & 1) asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(ot[j]));
+          else asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(ot[j] + laneOffE[ti]), "s"(rsrc4), "s"(baseS[ti]));
+          xr[ti][j >> 2][j & 3] = v;
+        }
+    };
+    u32x4 w3[CT];                                                       // w3 of (step, channel tile): one dwordx4 per lane
+    const int w3Lane = lane * 16;
+    auto issue_w3 = [&, rsrcW, w3Step](int s, int ct) {
+      if (NCHW_VAR & 16) asm volatile("v_mov_b32 %0, %1" : "=v"(w3[ct][0]) : "v"(s)); else
+      asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(w3[ct]) : "v"(w3Lane + (int)(s * w3Step)), "s"(rsrcW),
+                   "s"((uint32_t)((cc * CT + ct) * 1024)));
+    };
+    f32x4 acc[CT][IT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      const float b1 = p.bias[(cc * CT + ct) * 16 + li];
+#pragma unroll
+      for (int ti = 0; ti < IT; ++ti) acc[ct][ti] = f32x4{b1, b1, b1, b1};
+    }
+    // w1 / w2 of (step, channel tile) in LDS: 1 KB per piece, lane-contiguous 16-byte reads
+    const u32x4* __restrict__ wl = reinterpret_cast<const u32x4*>(ldsW) + (size_t)(cc * CT) * 128 + lane;
+    const int wStep = CTs * 128;                                        // u32x4 per step
+    issue_x(0);
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) issue_w3(0, ct);
+    // Outstanding loads are counted in issue order: at the top of step s the raw values of step s are followed by the six
+    // w3 loads of step s (vmcnt 6); before channel tile ct, its w3 load is followed by the w3 loads of tiles ct + 1 .. 5 of
+    // step s, the 32 operand loads of step s + 1 and the w3 loads of its tiles 0 .. ct - 1: 37 whatever ct
+    int s = 0;
+    do {
+      u32x4 bw[2][2];
+      bw[0][0] = wl[0]; bw[0][1] = wl[64];
+      split_wait<CT>(xr);
+      bf16x8 a1[IT], a2[IT], a3[IT];
+#pragma unroll
+      for (int ti = 0; ti < IT; ++ti) {
+        if (NCHW_VAR & 8) {
+          a1[ti] = __builtin_bit_cast(bf16x8, xr[ti][0]);
+          a2[ti] = a1[ti]; a3[ti] = a1[ti];
+        } else {
+          split_bf16x8(xr[ti], a1[ti], a2[ti], a3[ti]);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      issue_x(s + 1);                                                   // (the last step: the window's last element again, never used)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        if (ct + 1 < CT) { bw[(ct + 1) & 1][0] = wl[(ct + 1) * 128]; bw[(ct + 1) & 1][1] = wl[(ct + 1) * 128 + 64]; }
+        split_wait<CT - 1 + 8 * IT>(w3[ct]);
+        const bf16x8 b1 = __builtin_bit_cast(bf16x8, bw[ct & 1][0]), b2 = __builtin_bit_cast(bf16x8, bw[ct & 1][1]);
+        const bf16x8 b3 = __builtin_bit_cast(bf16x8, w3[ct]);
+#define SPLIT_TERM(A, B)                                                                                               \
+  _Pragma("unroll") for (int ti = 0; ti < IT; ++ti)                                                                    \
+    if (NCHW_VAR & 2) asm volatile("" : "+v"(acc[ct][ti]) : "v"(A[ti]), "v"(B)); else                                  \
+    acc[ct][ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ti], B, acc[ct][ti], 0, 0, 0);
+        SPLIT_TERM(a3, b1) SPLIT_TERM(a2, b2) SPLIT_TERM(a1, b3) SPLIT_TERM(a2, b1) SPLIT_TERM(a1, b2) SPLIT_TERM(a1, b1)
+#undef SPLIT_TERM
+        __builtin_amdgcn_sched_barrier(0);
+        issue_w3(s + 1, ct);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      wl += wStep;
+    } while (++s < steps);
+    split_wait<0>(xr);                                                  // nothing in flight into registers the stores may reuse
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) split_wait<0>(w3[ct]);
+    {
+      const int nPos = (NCHW_VAR & 4) ? (p.Wo < 0 ? IT : 0) : min(IT, p.Wo - ocol);
+      float* __restrict__ dst = p.dst + (((size_t)panel * P + orow * p.Wo + ocol + (kg >> 1)) * p.Ct + li) * PANEL + it * 16 + 4 * (kg & 1);
+      if (p.relu) {
+#pragma unroll
+        for (int tp = 0; tp < IT / 2; ++tp)
+          if (tp * 2 + (kg >> 1) < nPos) {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                const int ti = tp * 2 + h;
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = (0.0f < acc[ct][ti][e]) ? acc[ct][ti][e] : 0.0f;
+                *reinterpret_cast<f32x4*>(dst + ((size_t)tp * 2 * p.Ct + (cc * CT + ct) * 16) * PANEL + 8 * h) = v;
+                __builtin_amdgcn_sched_barrier(0);
+              }
+          }
+      } else {
+#pragma unroll
+        for (int ti = 0; ti < IT; ++ti)
+          if ((ti >> 1) * 2 + (kg >> 1) < nPos) {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+              *reinterpret_cast<f32x4*>(dst + ((size_t)(ti >> 1) * 2 * p.Ct + (cc * CT + ct) * 16) * PANEL + 8 * (ti & 1)) = acc[ct][ti];
+          }
+      }
+    }
+   };
+    if (edge) body(std::true_type{}); else body(std::false_type{});
+  }
+}
+
+__device__ __forceinline__ float bf16_hi(float x, uint16_t* h) {      // round to nearest even (finite x); returns the piece as fp32
+  uint32_t u = __builtin_bit_cast(uint32_t, x);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  *h = (uint16_t)(u >> 16);
+  return __builtin_bit_cast(float, u & 0xffff0000u);
+}
+
+// rows: [kh][kw][1][rowStride] slot bytes; ctrd: [Cs][K]; out: w1 / w2 [step][S / 16][piece][64 lanes][8], then
+// w3 [step][S / 16][64 lanes][8] (bf16): lane (li, kg), element j = the code word of window element k = 32 step + 8 kg + j for
+// channel 16 tile + li, zero past the window; w = w1 + w2 + w3 exactly
+__global__ void k_decode_weights_split(const uint8_t* __restrict__ rows, const float* __restrict__ ctrd, uint16_t* __restrict__ out,
+                                       QkSlots sl, int knl, int Cin, int K, int Ct, int Kb, int S) {
+  const int total = Kb * S, CTs = S / 16;
+  uint16_t* __restrict__ out3 = out + (size_t)2 * total;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int j = i & 7, ln = (i >> 3) & 63, tile = (i >> 9) % CTs, step = (i >> 9) / CTs;
+    const int ch = 16 * tile + (ln & 15), k = 32 * step + 8 * (ln >> 4) + j;
+    float w = 0.0f;
+    if (ch < Ct && k < Cin * knl * knl) {
+      const int kw = k % knl, kh = (k / knl) % knl, c = k / (knl * knl);
+      const int slot = rows[(size_t)(kh * knl + kw) * sl.rowStride + qk_slot_entry(sl, 0, ch)];
+      w = ctrd[(size_t)c * K + qcnn_row_slot(slot)];
+    }
+    uint16_t h1, h2, h3;
+    const float r = w - bf16_hi(w, &h1);
+    (void)bf16_hi(r - bf16_hi(r, &h2), &h3);
+    const size_t blk = (size_t)(step * CTs + tile) * 2 * 512 + ln * 8 + j;
+    out[blk] = h1;
+    out[blk + 512] = h2;
+    out3[i] = h3;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // FC layers whose sub-spaces have ONE dim (a 1000-way classifier behind 4096 features: AlexNet / VGG-16 fc8, 16 code
 // words of one float each): a look-up there stands for one multiply-add, so the table build — 4096 sub-spaces x 16 code
 // words x 128 images per panel — is pure overhead.  out[c] = bias[c] + sum_k x[k] * w[k][c], w[k][c] = ctrd[k][asmt[k][c]].
@@ -735,6 +998,36 @@ hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st) {
   const int blocks = (int)std::min<long long>(256, items);           // (few items: one per workgroup, see `sparse`)
   const size_t shm = (size_t)(p.Kp + 4) * p.S * sizeof(float) + (size_t)(p.Kp / 4 + 4) * 16;
   auto kern = k_conv_dec_nchw<6, 4>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NCHW_WAVES), shm, st, p);
+  return hipGetLastError();
+}
+
+bool qk_conv_dec_nchw_split_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kb) {
+  int kp = 0, s = 0;
+  if (!qk_conv_dec_nchw_shape(Cin, grp, M, Ct, knl, pad, &kp, &s)) return false;
+  const int kb = (Cin * knl * knl + 31) / 32 * 32;            // steps of 32 k
+  if ((size_t)kb * Ct * 4 + (size_t)(kb + 32) * 4 > 160 * 1024) return false;   // w1 / w2 + offset table
+  *Kb = kb;
+  return true;
+}
+
+hipError_t qk_decode_weights_split(const uint8_t* rows, const float* ctrd, uint16_t* out, const QkSlots& sl, int knl, int Cin, int K,
+                                   int Ct, int Kb, hipStream_t st) {
+  const int total = Kb * Ct;
+  hipLaunchKernelGGL(k_decode_weights_split, dim3((total + 255) / 256), dim3(256), 0, st, rows, ctrd, out, sl, knl, Cin, K, Ct, Kb, Ct);
+  return hipGetLastError();
+}
+
+// p.Kr = Cin knl^2, p.Kp = qk_conv_dec_nchw_split_shape's Kb, p.S = Ct, p.wdec = qk_decode_weights_split's planes
+hipError_t qk_conv_dec_nchw_split(const DecParams& p, hipStream_t st) {
+  if (!p.srcNchw || p.pad != 0 || p.Ct % 96 || p.S != p.Ct || p.Kp % 32 || (unsigned long long)p.nImages * p.Cin * p.H * p.W * 4ull >= (1ull << 32))
+    return hipErrorInvalidValue;
+  const long long items = (long long)p.panels * p.Ho * ((p.Wo + 3) / 4) * ((p.live + 15) / 16) * (p.Ct / 96);
+  const int blocks = (int)std::min<long long>(256, items);
+  const size_t shm = (size_t)p.Kp * p.S * 4 + (size_t)(p.Kp + 32) * 4;
+  auto kern = k_conv_dec_nchw_split<6, 4>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NCHW_WAVES), shm, st, p);

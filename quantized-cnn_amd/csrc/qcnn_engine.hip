@@ -45,6 +45,7 @@ struct LayerShape {
   size_t offCbn = 0, cbnBytes = 0; int cbnBits = 0;            // FC: the assignments bit-packed as the .cbn payload holds them (file order
                                                                // [Ct][M], include/FileIO.h:128-166), read in place by the few-image kernel
   size_t offDecN = 0; int decNV = 0;                          // first layer: the same code words in k_conv_dec_nchw's order; decNV: its padded k (0: not eligible)
+  size_t offDecB = 0; int decBK = 0;                          // ... split into three bf16 pieces for k_conv_dec_nchw_split; decBK: its padded k (0: not eligible)
   size_t offDec = 0; int decKp = 0, decS = 0;                  // decoded code words (qcnn_decoded.hip): conv layer with one sub-space of
                                                                // <= 4 dims (decKp > 0), FC layer with one-dim sub-spaces (decKp = -1); 0: not eligible
   bool hasDmap = false;
@@ -86,6 +87,7 @@ struct QcnnCtx {
   int smallBatch = 1;                // QCNN_OPT_SMALL_BATCH: few-image kernels for batches <= kSmallBatchMax
   int hostChunk = 2;                 // QCNN_OPT_HOST_CHUNK: panels per chunk of a large qcnn_forward_host batch (0: one launch)
   int directDec = 1;                 // QCNN_OPT_DIRECT_DEC: a decoded first layer reads the NCHW input in place (k_conv_dec_nchw) on the fast path
+  int decSplit = 1;                  // QCNN_OPT_DEC_BF16SPLIT: ... with its products as fp32-accurate split-bf16 MFMAs (k_conv_dec_nchw_split)
   int packedFc = 0;                  // QCNN_OPT_PACKED_FC (default off: measured 0.056 against 0.035 ms for AlexNet fc6 at one image): the few-image FC kernel reads the bit-packed assignment stream in place
   int half8 = 1;                     // QCNN_OPT_HALF8: half-panel eight-wave workgroups where predicted faster (2: whenever eligible)
   int sym8 = 1;                      // QCNN_OPT_SYM8: eight-wave symmetric workgroups where predicted faster (2: whenever eligible)
@@ -251,8 +253,13 @@ int plan_arena(QcnnCtx* c) {
       s.decNV = 0;
       if (l == 0 && qk_conv_dec_nchw_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, d.padSiz, &s.decNV, &nS)) {
         s.offDecN = off; off = align_up(off + sizeof(float) * (size_t)s.decNV * nS, 256);
+        s.decBK = 0;
+        if (qk_conv_dec_nchw_split_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, d.padSiz, &s.decBK)) {   // derived like the copy above
+          s.offDecB = off; off = align_up(off + 6 * (size_t)s.decBK * Ct, 256);                           // w1, w2, w3: 2 bytes each
+        }
       } else {
         s.decNV = 0;
+        s.decBK = 0;
       }
     } else if (d.type == QCNN_FCNT && !s.hasDmap && qk_fc_dec_shape((int)fm_elems(c, l), s.M, s.Cs, Ct, &s.decS)) {
       s.decKp = -1;                   // FC layer with one-dim sub-spaces: [D][decS] decoded code words
@@ -456,7 +463,9 @@ int launch_layer(QcnnCtx* c, int l, const float* src, float* dst, int panels, bo
         if (inNchw) { q.Kr = d.knlSiz * d.knlSiz * a.c; q.Kp = s.decNV; q.S = b.c; }
         q.relu = fuseRelu ? 1 : 0; q.panels = panels; q.live = live;
         s.lastFrom = -3; s.lastZ = inNchw ? 2 : 1;        // reported by qcnn_get_layer_split as (-3, 1), NCHW in place: (-3, 2)
-        e = inNchw ? qk_conv_dec_nchw(q, st) : qk_conv_dec(q, st);
+        const bool splitBf16 = inNchw && c->decSplit && s.decBK > 0;   // fp32-accurate split-bf16 products (QCNN_OPT_DEC_BF16SPLIT)
+        if (splitBf16) { q.Kp = s.decBK; q.wdec = reinterpret_cast<const float*>(c->arena + s.offDecB); }
+        e = splitBf16 ? qk_conv_dec_nchw_split(q, st) : inNchw ? qk_conv_dec_nchw(q, st) : qk_conv_dec(q, st);
         if (e != hipErrorInvalidValue) break;             // (a map beyond the kernel's 32-bit byte offsets: the table kernel below)
       }
       ConvParams p;
@@ -964,6 +973,7 @@ int qcnn_set_option(QcnnCtx* c, int option, int value) {
     case QCNN_OPT_SYM8: if (value < 0 || value > 3) return fail(c, "QCNN_OPT_SYM8 must be 0 (off), 1 (planner), 2 (forced tile form) or 3 (forced sliding form)"); c->sym8 = value; return 0;
     case QCNN_OPT_PACKED_FC: c->packedFc = value ? 1 : 0; return 0;
     case QCNN_OPT_DIRECT_DEC: c->directDec = value ? 1 : 0; return 0;
+    case QCNN_OPT_DEC_BF16SPLIT: c->decSplit = value ? 1 : 0; return 0;
     case QCNN_OPT_SYM: if (value < 0 || value > 2) return fail(c, "QCNN_OPT_SYM must be 0 (off), 1 (planner) or 2 (forced)"); c->sym = value; return 0;
     case QCNN_OPT_SLIDE: if (value < 0 || value > 2) return fail(c, "QCNN_OPT_SLIDE must be 0 (off), 1 (planner) or 2 (forced)"); c->slide = value; return 0;
     case QCNN_OPT_HOST_CHUNK:
@@ -1364,6 +1374,10 @@ hipError_t build_program(QcnnCtx* c, int layer, const QkSlots& sl) {
     e = qk_decode_weights_nchw(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<const float*>(c->arena + s.offCtrd),
                                reinterpret_cast<float*>(c->arena + s.offDecN), sl, d.knlSiz, c->dims[layer].c, s.K,
                                c->dims[layer + 1].c, s.decNV, c->dims[layer + 1].c, c->stream);
+  if (e == hipSuccess && s.decKp > 0 && s.decNV && s.decBK)
+    e = qk_decode_weights_split(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<const float*>(c->arena + s.offCtrd),
+                                reinterpret_cast<uint16_t*>(c->arena + s.offDecB), sl, d.knlSiz, c->dims[layer].c, s.K,
+                                c->dims[layer + 1].c, s.decBK, c->stream);
   if (e == hipSuccess && s.progF8Bytes)        // eight-wave FC kernel: uint16 offsets in its channel order
     e = qk_build_program_fc8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<uint16_t*>(c->arena + s.offProgF8), sl,
                              c->dims[layer + 1].c, s.M, c->stream);

@@ -393,6 +393,12 @@ bool qk_conv_dec_nchw_shape(int Cin, int grp, int M, int Ct, int knl, int pad, i
 hipError_t qk_decode_weights_nchw(const uint8_t* rows, const float* ctrd, float* out, const QkSlots& sl, int knl, int Cin, int K,
                                   int Ct, int Kp, int S, hipStream_t st);
 hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st);   // p.Kr = Cin knl^2, p.Kp and p.S from qk_conv_dec_nchw_shape
+// Its fp32-accurate split-bf16 form (QCNN_OPT_DEC_BF16SPLIT): k padded to Kb = a multiple of 32; wdec = the code words split
+// into three bf16 pieces, w1 / w2 [Kb / 32][Ct / 16][2][64][8] then w3 [Kb / 32][Ct / 16][64][8] (Kb x Ct x 6 bytes)
+bool qk_conv_dec_nchw_split_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kb);
+hipError_t qk_decode_weights_split(const uint8_t* rows, const float* ctrd, uint16_t* out, const QkSlots& sl, int knl, int Cin, int K,
+                                   int Ct, int Kb, hipStream_t st);
+hipError_t qk_conv_dec_nchw_split(const DecParams& p, hipStream_t st);   // p.Kp = Kb, p.S = Ct
 // FC layer with one-dim sub-spaces through its decoded code words (qcnn_decoded.hip).  wdec: [D][S], S = Ct rounded up to 64
 struct FcDecParams {
   const float* src;      // [panels][D][128]
