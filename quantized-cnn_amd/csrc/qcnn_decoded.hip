@@ -530,6 +530,13 @@ __global__ void k_decode_weights_nchw(const uint8_t* __restrict__ rows, const fl
 // Operand loads are inline assembly with counted waits (see the f32 kernel): step s splits its raw values, issues step
 // s + 1's loads into the same registers, then runs its channel tiles, each followed by the w3 load of step s + 1.  The
 // sum per output — bias, then per step the six terms in fixed order — depends on nothing but the output, as before.
+// RUNS (the default where it fits, nchw_split_runs): k in RUN ORDER instead.  Every (channel, kernel row) of the window is
+// cut into nr = ceil(knl / 4) runs of 4 consecutive columns; run r of a row starts at column min(4 r, knl - 4), so that
+// the last run overlaps its predecessor instead of reaching past the row (knl 11: columns 0, 4, 7), and the code words of
+// the repeated columns are zero.  k = 4 run + e (e: the column in the run); a lane's 8 k of a step are two runs, each ONE
+// buffer_load_dwordx4 (dword aligned: a window row is any number of floats) — 8 loads per step instead of 32.  The LDS
+// table holds run offsets; runs past the last repeat it (code words zero).  Every read stays inside its window row.
+// Shapes whose run-ordered w1 / w2 do not fit LDS, and kernel rows shorter than 4 columns, keep the flat order.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -560,10 +567,22 @@ __device__ __forceinline__ void split_wait(f32x4 (&x)[4][2]) {
 template <int N>
 __device__ __forceinline__ void split_wait(u32x4& w) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w) : "n"(N)); }
 
-template <int CT, int IT>
+// runs per kernel row of the run order (k_conv_dec_nchw_split<.., RUNS>), 0: the flat order; Kb of either order
+static inline int nchw_split_kb(int Cin, int knl, int nr) { return nr ? (Cin * knl * nr + 7) / 8 * 32 : (Cin * knl * knl + 31) / 32 * 32; }
+static inline size_t nchw_split_lds(int Kb, int Ct, int nr) {    // w1 / w2 + the offset table (one step of slack behind it)
+  return (size_t)Kb * Ct * 4 + (size_t)(nr ? Kb / 4 + 8 : Kb + 32) * 4;
+}
+static int nchw_split_runs(int Cin, int knl, int Ct) {
+  if (knl < 4) return 0;
+  const int nr = (knl + 3) / 4;
+  return nchw_split_lds(nchw_split_kb(Cin, knl, nr), Ct, nr) <= 160 * 1024 ? nr : 0;
+}
+
+template <int CT, int IT, bool RUNS>
 __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecParams p) {
   static_assert(IT == 4 && CT == 6, "a product tile is 2 positions x 8 images, an item two pairs of positions x two image halves x 96 channels");
   extern __shared__ __attribute__((aligned(16))) float ldsW[];          // [steps][S / 16][piece 2][64 lanes][8 bf16], then int [Kp + 32]
+                                                                        // (RUNS: int [Kp / 4 + 8], one per run)
   const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
   const int P = p.Ho * p.Wo;
   const int steps = p.Kp >> 5;                                          // Kp: Cin knl^2 padded to a multiple of 32
@@ -575,10 +594,19 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
     const f32x4* __restrict__ wsrc = reinterpret_cast<const f32x4*>(p.wdec);
     f32x4* ldsW4 = reinterpret_cast<f32x4*>(ldsW);
     for (int i = threadIdx.x; i < wq; i += 64 * NCHW_WAVES) ldsW4[i] = wsrc[i];
-    for (int i = threadIdx.x; i < p.Kp + 32; i += 64 * NCHW_WAVES) {
-      const int k = min(i, p.Kr - 1);
-      const int kw = k % p.knl, kh = (k / p.knl) % p.knl, c = k / (p.knl * p.knl);
-      ldsOff[i] = (int)((uint32_t)c * planeBytes + (uint32_t)kh * rowBytes + (uint32_t)kw * 4u);
+    if constexpr (RUNS) {
+      const int nr = (p.knl + 3) >> 2, nRuns = p.Cin * p.knl * nr;
+      for (int i = threadIdx.x; i < (p.Kp >> 2) + 8; i += 64 * NCHW_WAVES) {
+        const int r = min(i, nRuns - 1);
+        const int kw = min(4 * (r % nr), p.knl - 4), kh = (r / nr) % p.knl, c = r / (nr * p.knl);
+        ldsOff[i] = (int)((uint32_t)c * planeBytes + (uint32_t)kh * rowBytes + (uint32_t)kw * 4u);
+      }
+    } else {
+      for (int i = threadIdx.x; i < p.Kp + 32; i += 64 * NCHW_WAVES) {
+        const int k = min(i, p.Kr - 1);
+        const int kw = k % p.knl, kh = (k / p.knl) % p.knl, c = k / (p.knl * p.knl);
+        ldsOff[i] = (int)((uint32_t)c * planeBytes + (uint32_t)kh * rowBytes + (uint32_t)kw * 4u);
+      }
     }
   }
   __syncthreads();
@@ -631,10 +659,26 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
         baseS[ti] = imgS * imgBytes + ((uint32_t)(r0 * p.W) + posS * (uint32_t)p.stride) * 4u;
       }
     }
-    const int* __restrict__ offT = ldsOff + 8 * kg;
+    const int* __restrict__ offT = ldsOff + (RUNS ? 2 : 8) * kg;
     f32x4 xr[IT][2];                                                    // raw operands of the next step
-    // the 8 x IT operand loads of step s (lane: k = 32 s + 8 kg + j)
+    // the operand loads of step s (lane: k = 32 s + 8 kg + j).  RUNS: 2 x IT, one dwordx4 per run (k = 4 run + e)
     auto issue_x = [&, rsrc4](int s) {
+      if constexpr (RUNS) {
+        typedef int i32x2_t __attribute__((ext_vector_type(2)));
+        const i32x2_t o = *reinterpret_cast<const i32x2_t*>(offT + 8 * s);
+#pragma unroll
+        for (int ti = 0; ti < IT; ++ti)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (NCHW_VAR & 1) {
+              float v;
+              asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(o[h]));
+              xr[ti][h] = f32x4{v, v, v, v};
+            } else
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(xr[ti][h]) : "v"(o[h] + laneOffE[ti]), "s"(rsrc4), "s"(baseS[ti]));
+          }
+        return;
+      }
       const i32x4_t o0 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s), o1 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s + 4);
       const int ot[8] = {o0[0], o0[1], o0[2], o0[3], o1[0], o1[1], o1[2], o1[3]};
 #pragma unroll
@@ -669,7 +713,8 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
     for (int ct = 0; ct < CT; ++ct) issue_w3(0, ct);
     // Outstanding loads are counted in issue order: at the top of step s the raw values of step s are followed by the six
     // w3 loads of step s (vmcnt 6); before channel tile ct, its w3 load is followed by the w3 loads of tiles ct + 1 .. 5 of
-    // step s, the 32 operand loads of step s + 1 and the w3 loads of its tiles 0 .. ct - 1: 37 whatever ct
+    // step s, the 32 (RUNS: 8) operand loads of step s + 1 and the w3 loads of its tiles 0 .. ct - 1: 37 (13) whatever ct
+    constexpr int xLoads = (RUNS ? 2 : 8) * IT;
     int s = 0;
     do {
       u32x4 bw[2][2];
@@ -691,7 +736,7 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
         if (ct + 1 < CT) { bw[(ct + 1) & 1][0] = wl[(ct + 1) * 128]; bw[(ct + 1) & 1][1] = wl[(ct + 1) * 128 + 64]; }
-        split_wait<CT - 1 + 8 * IT>(w3[ct]);
+        split_wait<CT - 1 + xLoads>(w3[ct]);
         const bf16x8 b1 = __builtin_bit_cast(bf16x8, bw[ct & 1][0]), b2 = __builtin_bit_cast(bf16x8, bw[ct & 1][1]);
         const bf16x8 b3 = __builtin_bit_cast(bf16x8, w3[ct]);
 #define SPLIT_TERM(A, B)                                                                                               \
@@ -751,18 +796,25 @@ __device__ __forceinline__ float bf16_hi(float x, uint16_t* h) {      // round t
 }
 
 // rows: [kh][kw][1][rowStride] slot bytes; ctrd: [Cs][K]; out: w1 / w2 [step][S / 16][piece][64 lanes][8], then
-// w3 [step][S / 16][64 lanes][8] (bf16): lane (li, kg), element j = the code word of window element k = 32 step + 8 kg + j for
-// channel 16 tile + li, zero past the window; w = w1 + w2 + w3 exactly
+// w3 [step][S / 16][64 lanes][8] (bf16): lane (li, kg), element j = the code word of k = 32 step + 8 kg + j for channel
+// 16 tile + li, zero past the window; w = w1 + w2 + w3 exactly.  nr = 0: k flat over the window; nr > 0: run order
+// (k_conv_dec_nchw_split<.., true>), k = 4 run + e, zero on the columns a row's last run repeats
 __global__ void k_decode_weights_split(const uint8_t* __restrict__ rows, const float* __restrict__ ctrd, uint16_t* __restrict__ out,
-                                       QkSlots sl, int knl, int Cin, int K, int Ct, int Kb, int S) {
+                                       QkSlots sl, int knl, int Cin, int K, int Ct, int Kb, int S, int nr) {
   const int total = Kb * S, CTs = S / 16;
   uint16_t* __restrict__ out3 = out + (size_t)2 * total;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int j = i & 7, ln = (i >> 3) & 63, tile = (i >> 9) % CTs, step = (i >> 9) / CTs;
     const int ch = 16 * tile + (ln & 15), k = 32 * step + 8 * (ln >> 4) + j;
     float w = 0.0f;
-    if (ch < Ct && k < Cin * knl * knl) {
-      const int kw = k % knl, kh = (k / knl) % knl, c = k / (knl * knl);
+    int kw = k % knl, kh = (k / knl) % knl, c = k / (knl * knl);
+    bool live = k < Cin * knl * knl;
+    if (nr) {
+      const int r = k >> 2, ri = r % nr;
+      kw = min(4 * ri, knl - 4) + (k & 3); kh = (r / nr) % knl; c = r / (nr * knl);
+      live = r < Cin * knl * nr && kw >= 4 * ri;
+    }
+    if (ch < Ct && live) {
       const int slot = rows[(size_t)(kh * knl + kw) * sl.rowStride + qk_slot_entry(sl, 0, ch)];
       w = ctrd[(size_t)c * K + qcnn_row_slot(slot)];
     }
@@ -1007,8 +1059,9 @@ hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st) {
 bool qk_conv_dec_nchw_split_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kb) {
   int kp = 0, s = 0;
   if (!qk_conv_dec_nchw_shape(Cin, grp, M, Ct, knl, pad, &kp, &s)) return false;
-  const int kb = (Cin * knl * knl + 31) / 32 * 32;            // steps of 32 k
-  if ((size_t)kb * Ct * 4 + (size_t)(kb + 32) * 4 > 160 * 1024) return false;   // w1 / w2 + offset table
+  const int nr = nchw_split_runs(Cin, knl, Ct);               // run order where it fits, else flat
+  const int kb = nchw_split_kb(Cin, knl, nr);                 // steps of 32 k
+  if (nchw_split_lds(kb, Ct, nr) > 160 * 1024) return false;  // w1 / w2 + offset table
   *Kb = kb;
   return true;
 }
@@ -1016,18 +1069,22 @@ bool qk_conv_dec_nchw_split_shape(int Cin, int grp, int M, int Ct, int knl, int 
 hipError_t qk_decode_weights_split(const uint8_t* rows, const float* ctrd, uint16_t* out, const QkSlots& sl, int knl, int Cin, int K,
                                    int Ct, int Kb, hipStream_t st) {
   const int total = Kb * Ct;
-  hipLaunchKernelGGL(k_decode_weights_split, dim3((total + 255) / 256), dim3(256), 0, st, rows, ctrd, out, sl, knl, Cin, K, Ct, Kb, Ct);
+  const int nr = nchw_split_runs(Cin, knl, Ct);
+  if (Kb != nchw_split_kb(Cin, knl, nr)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_decode_weights_split, dim3((total + 255) / 256), dim3(256), 0, st, rows, ctrd, out, sl, knl, Cin, K, Ct, Kb, Ct, nr);
   return hipGetLastError();
 }
 
 // p.Kr = Cin knl^2, p.Kp = qk_conv_dec_nchw_split_shape's Kb, p.S = Ct, p.wdec = qk_decode_weights_split's planes
 hipError_t qk_conv_dec_nchw_split(const DecParams& p, hipStream_t st) {
-  if (!p.srcNchw || p.pad != 0 || p.Ct % 96 || p.S != p.Ct || p.Kp % 32 || (unsigned long long)p.nImages * p.Cin * p.H * p.W * 4ull >= (1ull << 32))
+  const int nr = nchw_split_runs(p.Cin, p.knl, p.Ct);         // the order qk_decode_weights_split wrote
+  if (!p.srcNchw || p.pad != 0 || p.Ct % 96 || p.S != p.Ct || p.Kp != nchw_split_kb(p.Cin, p.knl, nr) ||
+      (unsigned long long)p.nImages * p.Cin * p.H * p.W * 4ull >= (1ull << 32))
     return hipErrorInvalidValue;
   const long long items = (long long)p.panels * p.Ho * ((p.Wo + 3) / 4) * ((p.live + 15) / 16) * (p.Ct / 96);
   const int blocks = (int)std::min<long long>(256, items);
-  const size_t shm = (size_t)p.Kp * p.S * 4 + (size_t)(p.Kp + 32) * 4;
-  auto kern = k_conv_dec_nchw_split<6, 4>;
+  const size_t shm = nchw_split_lds(p.Kp, p.S, nr);
+  auto kern = nr ? k_conv_dec_nchw_split<6, 4, true> : k_conv_dec_nchw_split<6, 4, false>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NCHW_WAVES), shm, st, p);

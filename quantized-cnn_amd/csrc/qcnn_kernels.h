@@ -394,7 +394,9 @@ hipError_t qk_decode_weights_nchw(const uint8_t* rows, const float* ctrd, float*
                                   int Ct, int Kp, int S, hipStream_t st);
 hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st);   // p.Kr = Cin knl^2, p.Kp and p.S from qk_conv_dec_nchw_shape
 // Its fp32-accurate split-bf16 form (QCNN_OPT_DEC_BF16SPLIT): k padded to Kb = a multiple of 32; wdec = the code words split
-// into three bf16 pieces, w1 / w2 [Kb / 32][Ct / 16][2][64][8] then w3 [Kb / 32][Ct / 16][64][8] (Kb x Ct x 6 bytes)
+// into three bf16 pieces, w1 / w2 [Kb / 32][Ct / 16][2][64][8] then w3 [Kb / 32][Ct / 16][64][8] (Kb x Ct x 6 bytes).  k is
+// in run order (runs of 4 columns of a kernel row, read with 16-byte loads) where that fits LDS and knl >= 4, else flat over
+// the window; Cin, knl and Ct decide which, the same way in all three functions
 bool qk_conv_dec_nchw_split_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kb);
 hipError_t qk_decode_weights_split(const uint8_t* rows, const float* ctrd, uint16_t* out, const QkSlots& sl, int knl, int Cin, int K,
                                    int Ct, int Kb, hipStream_t st);
