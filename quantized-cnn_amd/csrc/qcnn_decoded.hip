@@ -44,20 +44,46 @@ __host__ __device__ __forceinline__ int qk_dec_krow(int k, int Kr, int Kp) {
   return real >= last ? real : -1;
 }
 
-// rows: [kh][kw][M = 1][rowStride] slot bytes (QkSlots order); ctrd: [Cs][K]; out: [knl][Kp][S]
+// The code word the assignment of tap (kh, kw) names for output channel ch, input channel d of the sub-space.  rows:
+// [kh][kw][M = 1][rowStride] slot bytes (QkSlots order); ctrd: [Cs][K]
+__device__ __forceinline__ float code_word(const uint8_t* __restrict__ rows, const float* __restrict__ ctrd, const QkSlots& sl, int knl,
+                                           int K, int d, int kh, int kw, int ch) {
+  const int slot = rows[(size_t)(kh * knl + kw) * sl.rowStride + qk_slot_entry(sl, 0, ch)];
+  return ctrd[(size_t)d * K + qcnn_row_slot(slot)];             // qcnn_row_slot is its own inverse; M = 1: stage row = code word
+}
+
+// out: [knl][Kp][S]
 __global__ void k_decode_weights(const uint8_t* __restrict__ rows, const float* __restrict__ ctrd, float* __restrict__ out,
                                  QkSlots sl, int knl, int Cin, int K, int Ct, int Kp, int S) {
   const int total = knl * Kp * S;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int ch = i % S, k = qk_dec_krow((i / S) % Kp, knl * Cin, Kp), kh = i / (S * Kp);
-    float w = 0.0f;
-    if (ch < Ct && k >= 0) {
-      const int kw = k / Cin, d = k % Cin;
-      const int slot = rows[(size_t)(kh * knl + kw) * sl.rowStride + qk_slot_entry(sl, 0, ch)];
-      w = ctrd[(size_t)d * K + qcnn_row_slot(slot)];            // qcnn_row_slot is its own inverse; M = 1: stage row = code word
-    }
-    out[i] = w;
+    out[i] = ch < Ct && k >= 0 ? code_word(rows, ctrd, sl, knl, K, k % Cin, kh, k / Cin, ch) : 0.0f;
   }
+}
+
+// n16 16-byte words from global memory into LDS, by the THREADS threads of the workgroup
+template <int THREADS>
+__device__ __forceinline__ void lds_fill(float* lds, const float* __restrict__ src, int n16) {
+  const f32x4* __restrict__ src4 = reinterpret_cast<const f32x4*>(src);
+  f32x4* lds4 = reinterpret_cast<f32x4*>(lds);
+  for (int i = threadIdx.x; i < n16; i += THREADS) lds4[i] = src4[i];
+}
+
+// The items of wave `wave` of a persistent workgroup of WAVES: first, first + stride, ... below end.  Workgroups go to the
+// eight XCDs round-robin (workgroup i -> XCD i % 8) and every XCD has its own L2: an XCD takes a CONTIGUOUS eighth of the
+// item list (whole panels for a 1000-image batch), so that the windows its waves read overlap in ITS L2 instead of every L2
+// fetching the whole input.  SPREAD: a launch of less than one item per wave (a few images) spreads its items over the SIMDs
+// of ALL workgroups — wave w of workgroup g takes item w wgX + g — instead of filling the waves of a few: an item then has a
+// matrix pipe to itself
+struct ItemRange { int first, end, stride; };
+template <int WAVES, bool SPREAD>
+__device__ __forceinline__ ItemRange xcd_items(int nItems, int wave) {
+  const int xcd = blockIdx.x & 7, nX = gridDim.x < 8 ? gridDim.x : 8;
+  const int wgX = (gridDim.x - xcd + 7) >> 3;                           // workgroups of this XCD
+  const int itemBeg = (int)((long long)nItems * xcd / nX), itemEnd = (int)((long long)nItems * (xcd + 1) / nX);
+  const bool sparse = SPREAD && itemEnd - itemBeg <= wgX * WAVES;
+  return {itemBeg + (sparse ? wave * wgX + (int)(blockIdx.x >> 3) : (int)(blockIdx.x >> 3) * WAVES + wave), itemEnd, wgX * WAVES};
 }
 
 // Persistent waves: a workgroup loads ALL decoded code words into LDS once ([knl * Kp][S], <= 152 KB), then every wave
@@ -78,12 +104,7 @@ __global__ __launch_bounds__(1024) void k_conv_dec(DecParams p) {
   extern __shared__ __attribute__((aligned(16))) float ldsW[];          // [knl * Kp][S]
   const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
   const int P = p.Ho * p.Wo;
-  {
-    const int wq = (p.knl * p.Kp * p.S) >> 2;
-    const f32x4* __restrict__ wsrc = reinterpret_cast<const f32x4*>(p.wdec);
-    f32x4* ldsW4 = reinterpret_cast<f32x4*>(ldsW);
-    for (int i = threadIdx.x; i < wq; i += 1024) ldsW4[i] = wsrc[i];
-  }
+  lds_fill<1024>(ldsW, p.wdec, (p.knl * p.Kp * p.S) >> 2);
   __syncthreads();
   const int NS = p.Kp >> 2;                                             // steps (of four k) per kernel row
   const int T = p.knl * NS;                                             // steps per work item
@@ -93,13 +114,8 @@ __global__ __launch_bounds__(1024) void k_conv_dec(DecParams p) {
   const int chunks = p.Ct / (16 * CT);                                  // channel chunks
   const int nItems = p.panels * groups * halves * chunks;
   const int kClamp = p.Kr - 1;
-  // Workgroups go to the eight XCDs round-robin (workgroup i -> XCD i % 8) and every XCD has its own L2: an XCD takes a
-  // CONTIGUOUS eighth of the item list (whole panels for a 1000-image batch), so that the windows its waves read overlap
-  // in ITS L2 instead of every L2 fetching the whole input.
-  const int xcd = blockIdx.x & 7, nX = gridDim.x < 8 ? gridDim.x : 8;
-  const int wgX = (gridDim.x - xcd + 7) >> 3;                           // workgroups of this XCD
-  const int itemBeg = (int)((long long)nItems * xcd / nX), itemEnd = (int)((long long)nItems * (xcd + 1) / nX);
-  for (int item = itemBeg + (blockIdx.x >> 3) * 16 + wave; item < itemEnd; item += wgX * 16) {
+  const ItemRange ir = xcd_items<16, false>(nItems, wave);
+  for (int item = ir.first; item < ir.end; item += ir.stride) {
     // The lane-derived address parts are RE-DERIVED per item from an opaque copy of the lane id: as loop invariants they
     // would have to live through the whole item loop beside 96 accumulator registers, and the compiler spilled two of
     // them to scratch (a handful of vector instructions per ~76 000-cycle item instead).
@@ -260,17 +276,21 @@ __global__ __launch_bounds__(1024) void k_conv_dec(DecParams p) {
   }
 }
 
+// launch with shm bytes of dynamic LDS (above the default limit: raised first)
+template <typename Params>
+hipError_t launch_lds(void (*kern)(Params), dim3 grid, dim3 block, size_t shm, hipStream_t st, const Params& p) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, grid, block, shm, st, p);
+  return hipGetLastError();
+}
+
 template <int CT, int PW, bool PADDED, int R, int IT>
 hipError_t launch_dec(const DecParams& p, hipStream_t st) {
   const int P = p.Ho * p.Wo;
   const long long items = (long long)p.panels * ((P + PW - 1) / PW) * ((p.live + 16 * IT - 1) / (16 * IT)) * (p.Ct / (16 * CT));
   const int blocks = (int)std::min<long long>(256, (items + 15) / 16);    // one persistent workgroup per CU
-  const size_t shm = (size_t)p.knl * p.Kp * p.S * sizeof(float);
-  auto kern = k_conv_dec<CT, PW, PADDED, R, IT>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(1024), shm, st, p);
-  return hipGetLastError();
+  return launch_lds(k_conv_dec<CT, PW, PADDED, R, IT>, dim3(blocks), dim3(1024), (size_t)p.knl * p.Kp * p.S * sizeof(float), st, p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -299,130 +319,205 @@ hipError_t launch_dec(const DecParams& p, hipStream_t st) {
 //   (whole 128-byte lines per wave) 1.82
 // the matrix pipe alone would need 1.42 ms at 2.4 GHz; what is left is the stores and loads of a wave's item boundary that
 // its SIMD neighbour's products do not cover.
+// The split-bf16 kernel further down has the same tile, items, clamps and stores: the helpers below are both kernels'.
 // ------------------------------------------------------------------------------------------------------------------
-// s_waitcnt vmcnt(N) that the operands of a step pass through (the compiler must not move their uses above it)
-template <int N, int IT>
-__device__ __forceinline__ void nchw_wait_impl(float (&bb)[IT]) {
-  if constexpr (IT == 4) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(bb[0]), "+v"(bb[1]), "+v"(bb[2]), "+v"(bb[3]) : "n"(N));
-  else if constexpr (IT == 5) asm volatile("s_waitcnt vmcnt(%5)" : "+v"(bb[0]), "+v"(bb[1]), "+v"(bb[2]), "+v"(bb[3]), "+v"(bb[4]) : "n"(N));
-  else asm volatile("s_waitcnt vmcnt(%6)" : "+v"(bb[0]), "+v"(bb[1]), "+v"(bb[2]), "+v"(bb[3]), "+v"(bb[4]), "+v"(bb[5]) : "n"(N));
-}
-template <int N, int IT>
-__device__ __forceinline__ void nchw_wait(float (&bb)[IT]) { nchw_wait_impl<N, IT>(bb); }
-
 #ifndef NCHW_WAVES
 #define NCHW_WAVES 8
 #endif
+#ifndef NCHW_VAR
+#define NCHW_VAR 0      // timing experiments (scripts/variants_nchw.sh): 1 no operand loads, 2 no products, 4 no stores,
+#endif                  // 8 no split, 16 no w3 loads (the last two: k_conv_dec_nchw_split)
+
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+
+// buffer resource for the inline-assembly loads: base, stride 0, `bytes` (at most 2^32 - 1), raw 32-bit data format
+__device__ __forceinline__ i32x4_t raw_rsrc(const void* base, unsigned long long bytes) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+  return i32x4_t{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xffffu), (int)(bytes < 0xffffffffull ? (unsigned)bytes : 0xffffffffu),
+                 0x00020000};
+}
+
+// byte offset of element (c, kh, kw) of a window from the window's corner in an NCHW image
+__device__ __forceinline__ int nchw_win_off(const DecParams& p, int c, int kh, int kw) {
+  return (int)((uint32_t)c * ((uint32_t)p.H * p.W * 4u) + (uint32_t)kh * ((uint32_t)p.W * 4u) + (uint32_t)kw * 4u);
+}
+
+// offset table of k flat over the window, n entries: k = (c knl + kh) knl + kw; past the window the last element again
+__device__ __forceinline__ void nchw_flat_offsets(const DecParams& p, int* ldsOff, int n) {
+  for (int i = threadIdx.x; i < n; i += 64 * NCHW_WAVES) {
+    const int k = min(i, p.Kr - 1);                                     // Kr: Cin knl^2
+    ldsOff[i] = nchw_win_off(p, k / (p.knl * p.knl), (k / p.knl) % p.knl, k % p.knl);
+  }
+}
+
+// The item list of a launch: image tiles of 16 images x channel chunks of 16 CT x position groups of IT consecutive
+// positions of an output row x panels
+struct NchwGrid {
+  uint32_t imgBytes;                                                    // one image, Cin H W floats
+  int tiles, chunks, WoG, PG, nItems;
+};
+template <int CT, int IT>
+__device__ __forceinline__ NchwGrid nchw_grid(const DecParams& p) {
+  const int tiles = (p.live + 15) / 16;                                 // image tiles a panel has (a small batch: fewer)
+  const int chunks = p.Ct / (16 * CT);
+  const int WoG = (p.Wo + IT - 1) / IT, PG = p.Ho * WoG;                // position groups: IT consecutive positions of an output row
+  return {(uint32_t)p.Cin * p.H * p.W * 4u, tiles, chunks, WoG, PG, p.panels * PG * tiles * chunks};
+}
+
+// One work item of a wave, and its lane's place in it
+struct NchwItem {
+  int laneI, li, kq;                                                    // lane = 16 kq + li; laneI: the same, opaque
+  int it, cc, panel, orow, ocol, r0;
+  uint32_t img0;                                                        // the tile's first image in the batch
+  bool edge;
+  int laneOff;                                                          // lane row li of a product tile, from the tile's first row
+  uint32_t base0;                                                       // corner of image tile 0's window in the batch
+};
+template <int IT>
+__device__ __forceinline__ NchwItem nchw_item(const DecParams& p, const NchwGrid& g, int item, int lane) {
+  int laneI = lane;
+  asm volatile("" : "+v"(laneI));                                       // lane-derived constants re-derived per item (registers)
+  const int li = laneI & 15, kq = laneI >> 4;
+  // image tiles fastest: the eight waves of a workgroup write the 128 images of the same (position, channel) rows at about
+  // the same time, so that L2 sees whole lines (position groups fastest: 2.03 against 1.98 ms with dword stores)
+  const int it = item % g.tiles, cc = (item / g.tiles) % g.chunks, pg = (item / (g.tiles * g.chunks)) % g.PG, panel = item / (g.chunks * g.tiles * g.PG);
+  const int orow = pg / g.WoG, ocol = (pg % g.WoG) * IT;
+  const int r0 = orow * p.stride, c0 = ocol * p.stride;                 // unpadded layers
+  const uint32_t img0 = (uint32_t)(p.panel0 + panel) * PANEL + (uint32_t)it * 16u;
+  // row li of a product tile: image li & 7 of the tile's eight, position li >> 3 of its two.  Positions past the end of the
+  // output row read columns of the next image row, of the next plane, of the next image ... finite values, never stored.
+  // That stays inside the caller's buffer as long as an image FOLLOWS the tile's sixteen.  An item that holds the batch's
+  // last image or images past it (a ragged last panel launches all eight image tiles) takes the `edge` form of the body
+  // (nchw_tile_bases).
+  const bool edge = img0 + 16u >= (uint32_t)p.nImages;
+  const int laneOff = (int)((uint32_t)(li & 7) * g.imgBytes + (uint32_t)((li >> 3) * p.stride) * 4u);
+  const uint32_t base0 = img0 * g.imgBytes + (uint32_t)(r0 * p.W + c0) * 4u;
+  return {laneI, li, kq, it, cc, panel, orow, ocol, r0, img0, edge, laneOff, base0};
+}
+
+// Lane part (vector offset) and scalar base of image tile ti's loads: 8 (ti & 1) images and 2 (ti >> 1) positions on from
+// tile 0.  EDGE: every image index is clamped to the last image and every position to the last of its output row — in the
+// scalar offset AND per lane —, so that no address leaves the batch whatever the buffer's range check does with the scalar
+// offset (the gfx9 raw-buffer check covers the vector offset only), and (last image) x imgBytes cannot wrap 32 bits.  Those
+// lanes' results are never stored / never read.
+template <bool EDGE, int IT>
+__device__ __forceinline__ void nchw_tile_bases(const DecParams& p, const NchwGrid& g, const NchwItem& w, int (&laneOffT)[IT],
+                                                uint32_t (&baseT)[IT]) {
+#pragma unroll
+  for (int ti = 0; ti < IT; ++ti) {
+    laneOffT[ti] = w.laneOff;
+    baseT[ti] = w.base0 + (uint32_t)(ti & 1) * 8u * g.imgBytes + (uint32_t)((ti >> 1) * 2 * p.stride) * 4u;
+  }
+  if constexpr (EDGE) {
+    const uint32_t lastImg = (uint32_t)p.nImages - 1u, lastPos = (uint32_t)p.Wo - 1u;
+#pragma unroll
+    for (int ti = 0; ti < IT; ++ti) {
+      const uint32_t imgS = min(w.img0 + 8u * (uint32_t)(ti & 1), lastImg), imgL = min(w.img0 + 8u * (uint32_t)(ti & 1) + (uint32_t)(w.li & 7), lastImg);
+      const uint32_t posS = min((uint32_t)w.ocol + 2u * (uint32_t)(ti >> 1), lastPos), posL = min((uint32_t)w.ocol + 2u * (uint32_t)(ti >> 1) + (uint32_t)(w.li >> 3), lastPos);
+      laneOffT[ti] = (int)((imgL - imgS) * g.imgBytes + (posL - posS) * (uint32_t)p.stride * 4u);
+      baseT[ti] = imgS * g.imgBytes + ((uint32_t)(w.r0 * p.W) + posS * (uint32_t)p.stride) * 4u;
+    }
+  }
+}
+
+template <int CT, int IT>
+__device__ __forceinline__ void nchw_bias(const DecParams& p, const NchwItem& w, f32x4 (&acc)[CT][IT]) {
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    const float b1 = p.bias[(w.cc * CT + ct) * 16 + w.li];
+#pragma unroll
+    for (int ti = 0; ti < IT; ++ti) acc[ct][ti] = f32x4{b1, b1, b1, b1};
+  }
+}
+
+// The image values are the rows of a product (A), the code words its columns (B): lane (li, kq) holds channel li of the tile
+// at position kq >> 1 of the tile's two for the FOUR CONSECUTIVE images 4 (kq & 1) .. + 3 of its eight — one 16-byte store
+// per tile
+template <int CT, int IT>
+__device__ __forceinline__ void nchw_store(const DecParams& p, const NchwItem& w, const f32x4 (&acc)[CT][IT]) {
+  const int nPos = (NCHW_VAR & 4) ? (p.Wo < 0 ? IT : 0) : min(IT, p.Wo - w.ocol);
+  float* __restrict__ dst = p.dst + (((size_t)w.panel * (p.Ho * p.Wo) + w.orow * p.Wo + w.ocol + (w.kq >> 1)) * p.Ct + w.li) * PANEL +
+                            w.it * 16 + 4 * (w.kq & 1);
+  // two copies of the store loop under one uniform branch: a ReLU applied under a branch INSIDE the loop made the compiler
+  // keep a second set of result registers (225 instead of 140)
+  if (p.relu) {
+    // the two halves (images 0-7, 8-15) of a row's 64 bytes leave back to back (1.81 -> 1.79 ms)
+#pragma unroll
+    for (int tp = 0; tp < IT / 2; ++tp)
+      if (tp * 2 + (w.kq >> 1) < nPos) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int ti = tp * 2 + h;
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = (0.0f < acc[ct][ti][e]) ? acc[ct][ti][e] : 0.0f;
+            *reinterpret_cast<f32x4*>(dst + ((size_t)tp * 2 * p.Ct + (w.cc * CT + ct) * 16) * PANEL + 8 * h) = v;
+            __builtin_amdgcn_sched_barrier(0);
+          }
+      }
+  } else {
+#pragma unroll
+    for (int ti = 0; ti < IT; ++ti)
+      if ((ti >> 1) * 2 + (w.kq >> 1) < nPos) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+          *reinterpret_cast<f32x4*>(dst + ((size_t)(ti >> 1) * 2 * p.Ct + (w.cc * CT + ct) * 16) * PANEL + 8 * (ti & 1)) = acc[ct][ti];
+      }
+  }
+}
+
+// s_waitcnt vmcnt(N) that the operands of a step pass through (the compiler must not move their uses above it)
+template <int N>
+__device__ __forceinline__ void nchw_wait(float (&bb)[4]) {
+  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(bb[0]), "+v"(bb[1]), "+v"(bb[2]), "+v"(bb[3]) : "n"(N));
+}
+
 template <int CT, int IT>
 __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw(DecParams p) {
   static_assert(IT == 4, "a product tile is 2 positions x 8 images, an item two pairs of positions x two image halves");
   extern __shared__ __attribute__((aligned(16))) float ldsW[];          // [steps][Ct / 16][4 k][16]: a wave's read of one channel tile is
                                                                         // 64 consecutive floats (no bank conflicts); then int [steps + 4][4]
   const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
-  const int P = p.Ho * p.Wo;
   const int steps = p.Kp >> 2;                                          // Kp: Cin knl^2 padded to a multiple of 16
-  const uint32_t imgBytes = (uint32_t)p.Cin * p.H * p.W * 4u, planeBytes = (uint32_t)p.H * p.W * 4u, rowBytes = (uint32_t)p.W * 4u;
   // (one step of slack behind the code words: the last step of an item pre-loads "the next step's" code words, which nobody
   // uses — the offset table sits behind that slack, inside the allocation)
   int* ldsOff = reinterpret_cast<int*>(ldsW + (size_t)(steps + 1) * 4 * p.S);
-  {
-    const int wq = steps * p.S;
-    const f32x4* __restrict__ wsrc = reinterpret_cast<const f32x4*>(p.wdec);
-    f32x4* ldsW4 = reinterpret_cast<f32x4*>(ldsW);
-    for (int i = threadIdx.x; i < wq; i += 64 * NCHW_WAVES) ldsW4[i] = wsrc[i];
-    for (int i = threadIdx.x; i < (steps + 4) * 4; i += 64 * NCHW_WAVES) {
-      const int k = min(i, p.Kr - 1);                                   // Kr: Cin knl^2
-      const int kw = k % p.knl, kh = (k / p.knl) % p.knl, c = k / (p.knl * p.knl);
-      ldsOff[i] = (int)((uint32_t)c * planeBytes + (uint32_t)kh * rowBytes + (uint32_t)kw * 4u);
-    }
-  }
+  lds_fill<64 * NCHW_WAVES>(ldsW, p.wdec, steps * p.S);
+  nchw_flat_offsets(p, ldsOff, (steps + 4) * 4);
   __syncthreads();
-  const int tiles = (p.live + 15) / 16;                                 // image tiles a panel has (a small batch: fewer)
-  const int chunks = p.Ct / (16 * CT);
-  const int WoG = (p.Wo + IT - 1) / IT, PG = p.Ho * WoG;                // position groups: IT consecutive positions of an output row
-  const int nItems = p.panels * PG * tiles * chunks;
-  const unsigned long long total = (unsigned long long)p.nImages * imgBytes;
-  typedef int i32x4_t __attribute__((ext_vector_type(4)));
-  const unsigned long long srcA = reinterpret_cast<unsigned long long>(p.src);
-  // buffer resource: base, stride 0, the batch's bytes, raw 32-bit data format.  No load below depends on the range check:
-  // every address is inside the batch by construction (see `edge`)
-  const i32x4_t rsrc4 = {(int)(unsigned)srcA, (int)((unsigned)(srcA >> 32) & 0xffffu),
-                         (int)(total < 0xffffffffull ? (unsigned)total : 0xffffffffu), 0x00020000};
-  const int xcd = blockIdx.x & 7, nX = gridDim.x < 8 ? gridDim.x : 8;
-  const int wgX = (gridDim.x - xcd + 7) >> 3;
-  const int itemBeg = (int)((long long)nItems * xcd / nX), itemEnd = (int)((long long)nItems * (xcd + 1) / nX);
-  // a launch of less than one item per wave (a few images) spreads its items over the SIMDs of ALL workgroups — wave w of
-  // workgroup g takes item w wgX + g — instead of filling the eight waves of a few: an item then has a matrix pipe to itself
-  const bool sparse = itemEnd - itemBeg <= wgX * NCHW_WAVES;
-  for (int item = itemBeg + (sparse ? wave * wgX + (int)(blockIdx.x >> 3) : (int)(blockIdx.x >> 3) * NCHW_WAVES + wave); item < itemEnd;
-       item += wgX * NCHW_WAVES) {
-    int laneI = lane;
-    asm volatile("" : "+v"(laneI));                                     // lane-derived constants re-derived per item (registers)
-    const int li = laneI & 15, kq = laneI >> 4;
-    // image tiles fastest: the eight waves of a workgroup write the 128 images of the same (position, channel) rows at about
-    // the same time, so that L2 sees whole lines (position groups fastest: 2.03 against 1.98 ms with dword stores)
-    const int it = item % tiles, cc = (item / tiles) % chunks, pg = (item / (tiles * chunks)) % PG, panel = item / (chunks * tiles * PG);
-    const int orow = pg / WoG, ocol = (pg % WoG) * IT;
-    const int r0 = orow * p.stride, c0 = ocol * p.stride;                        // unpadded layers
-    const uint32_t img0 = (uint32_t)(p.panel0 + panel) * PANEL + (uint32_t)it * 16u;
-    // row li of a product tile: image li & 7 of the tile's eight, position li >> 3 of its two.  Positions past the end of the
-    // output row read columns of the next image row, of the next plane, of the next image ... finite values, never stored.
-    // That stays inside the caller's buffer as long as an image FOLLOWS the tile's sixteen.  An item that holds the batch's
-    // last image or images past it (a ragged last panel launches all eight image tiles) takes the `edge` form of the body:
-    // every image index is clamped to the last image and every position to the last of its output row — in the scalar offset
-    // AND per lane —, so that no address leaves the batch whatever the buffer's range check does with the scalar offset (the
-    // gfx9 raw-buffer check covers the vector offset only), and (last image) x imgBytes cannot wrap 32 bits.  Those lanes'
-    // results are never stored / never read.
-    const bool edge = img0 + 16u >= (uint32_t)p.nImages;
-    const int laneOff = (int)((uint32_t)(li & 7) * imgBytes + (uint32_t)((li >> 3) * p.stride) * 4u);
-    const uint32_t base0 = img0 * imgBytes + (uint32_t)(r0 * p.W + c0) * 4u;      // tile ti: + 8 (ti & 1) images, + 2 (ti >> 1) positions
-    const int* __restrict__ offT = ldsOff + kq;
+  const NchwGrid g = nchw_grid<CT, IT>(p);
+  // No load below depends on the buffer's range check: every address is inside the batch by construction (see `edge`)
+  const i32x4_t rsrc4 = raw_rsrc(p.src, (unsigned long long)p.nImages * g.imgBytes);
+  const ItemRange ir = xcd_items<NCHW_WAVES, true>(g.nItems, wave);
+  for (int item = ir.first; item < ir.end; item += ir.stride) {
+    const NchwItem w = nchw_item<IT>(p, g, item, lane);
+    const int* __restrict__ offT = ldsOff + w.kq;
    auto body = [&](auto edgeTag) {
-    constexpr bool EDGE = decltype(edgeTag)::value;
-    int laneOffE[IT];
-    uint32_t baseE[IT];
-    if constexpr (EDGE) {
-      const uint32_t lastImg = (uint32_t)p.nImages - 1u, lastPos = (uint32_t)p.Wo - 1u;
-#pragma unroll
-      for (int ti = 0; ti < IT; ++ti) {
-        const uint32_t imgS = min(img0 + 8u * (uint32_t)(ti & 1), lastImg), imgL = min(img0 + 8u * (uint32_t)(ti & 1) + (uint32_t)(li & 7), lastImg);
-        const uint32_t posS = min((uint32_t)ocol + 2u * (uint32_t)(ti >> 1), lastPos), posL = min((uint32_t)ocol + 2u * (uint32_t)(ti >> 1) + (uint32_t)(li >> 3), lastPos);
-        laneOffE[ti] = (int)((imgL - imgS) * imgBytes + (posL - posS) * (uint32_t)p.stride * 4u);
-        baseE[ti] = imgS * imgBytes + ((uint32_t)(r0 * p.W) + posS * (uint32_t)p.stride) * 4u;
-      }
-    }
+    int laneOffT[IT];
+    uint32_t baseT[IT];
+    nchw_tile_bases<decltype(edgeTag)::value>(p, g, w, laneOffT, baseT);
     // Operand loads as inline assembly with counted waits: the compiler's own vmcnt bookkeeping drains the ring to one
     // step at every loop back edge (s_waitcnt vmcnt(4) in front of the first of four steps).  Loads return in order, so
     // "at most 12 outstanding" = everything but the three newest steps has arrived — whatever else (the previous item's
     // stores) is still in flight only makes the wait stricter.
-#ifndef NCHW_VAR
-#define NCHW_VAR 0                      // timing experiments (scripts/variants_nchw.sh): 1 no operand loads, 2 no products, 4 no stores
-#endif
-    auto issue = [&, rsrc4, base0](int s, float (&bb)[IT]) {             // the operands of step s (explicit captures: asm operands inside a generic lambda)
+    auto issue = [&, rsrc4](int s, float (&bb)[IT]) {                  // the operands of step s (explicit capture: asm operand inside a generic lambda)
       const int ot = offT[s * 4];
-      const int vo = ot + laneOff;
-      (void)base0;
 #pragma unroll
       for (int ti = 0; ti < IT; ++ti)
-        if (NCHW_VAR & 1) asm volatile("v_mov_b32 %0, %1" : "=v"(bb[ti]) : "v"(vo)); else if constexpr (EDGE)
-        asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(bb[ti]) : "v"(ot + laneOffE[ti]), "s"(rsrc4), "s"(baseE[ti])); else
-        asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(bb[ti]) : "v"(vo), "s"(rsrc4),
-                     "s"(base0 + (uint32_t)(ti & 1) * 8u * imgBytes + (uint32_t)((ti >> 1) * 2 * p.stride) * 4u));
+        if (NCHW_VAR & 1) asm volatile("v_mov_b32 %0, %1" : "=v"(bb[ti]) : "v"(ot + w.laneOff)); else
+        asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(bb[ti]) : "v"(ot + laneOffT[ti]), "s"(rsrc4), "s"(baseT[ti]));
     };
     f32x4 acc[CT][IT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const float b1 = p.bias[(cc * CT + ct) * 16 + li];
-#pragma unroll
-      for (int ti = 0; ti < IT; ++ti) acc[ct][ti] = f32x4{b1, b1, b1, b1};
-    }
-    const float* __restrict__ wl = ldsW + cc * 64 * CT + laneI;
+    nchw_bias(p, w, acc);
+    const float* __restrict__ wl = ldsW + w.cc * 64 * CT + w.laneI;
     const int aStep = 4 * p.S;
     float a[2][CT], b[4][IT];                                           // b: a ring of four steps' operands, three in flight (a ring
                                                                         // of eight: no faster)
-    auto load_a = [&](const float* __restrict__ w, float (&aa)[CT]) {
+    auto load_a = [&](const float* __restrict__ wp, float (&aa)[CT]) {
 #pragma unroll
-      for (int ct = 0; ct < CT; ++ct) aa[ct] = w[ct * 64];
+      for (int ct = 0; ct < CT; ++ct) aa[ct] = wp[ct * 64];
     };
     issue(0, b[0]);
     issue(1, b[1]);
@@ -455,43 +550,9 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw(DecParams p) 
     NCHW_WAIT(0, b[0]); NCHW_WAIT(0, b[1]); NCHW_WAIT(0, b[2]);         // nothing in flight into registers the stores may reuse
 #undef NCHW_STEP
 #undef NCHW_WAIT
-    // The image values are the A operand, the code words B (the lane layouts of the two operands of a 16x16x4 instruction
-    // are the same: this is the order of the arguments only): lane (li, kq) holds channel li of the tile at position kq >> 1
-    // of the tile's two for the FOUR CONSECUTIVE images 4 (kq & 1) .. + 3 of its eight — one 16-byte store per tile
-    {
-      const int nPos = (NCHW_VAR & 4) ? (p.Wo < 0 ? IT : 0) : min(IT, p.Wo - ocol);
-      float* __restrict__ dst = p.dst + (((size_t)panel * P + orow * p.Wo + ocol + (kq >> 1)) * p.Ct + li) * PANEL + it * 16 + 4 * (kq & 1);
-      // two copies of the store loop under one uniform branch: a ReLU applied under a branch INSIDE the loop made the compiler
-      // keep a second set of result registers (225 instead of 140)
-      if (p.relu) {
-        // the two halves (images 0-7, 8-15) of a row's 64 bytes leave back to back (1.81 -> 1.79 ms)
-#pragma unroll
-        for (int tp = 0; tp < IT / 2; ++tp)
-          if (tp * 2 + (kq >> 1) < nPos) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-              for (int h = 0; h < 2; ++h) {
-                const int ti = tp * 2 + h;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = (0.0f < acc[ct][ti][e]) ? acc[ct][ti][e] : 0.0f;
-                *reinterpret_cast<f32x4*>(dst + ((size_t)tp * 2 * p.Ct + (cc * CT + ct) * 16) * PANEL + 8 * h) = v;
-                __builtin_amdgcn_sched_barrier(0);
-              }
-          }
-      } else {
-#pragma unroll
-        for (int ti = 0; ti < IT; ++ti)
-          if ((ti >> 1) * 2 + (kq >> 1) < nPos) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-              *reinterpret_cast<f32x4*>(dst + ((size_t)(ti >> 1) * 2 * p.Ct + (cc * CT + ct) * 16) * PANEL + 8 * (ti & 1)) = acc[ct][ti];
-          }
-      }
-    }
+    nchw_store(p, w, acc);
    };
-    if (edge) body(std::true_type{}); else body(std::false_type{});
+    if (w.edge) body(std::true_type{}); else body(std::false_type{});
   }
 }
 
@@ -503,13 +564,7 @@ __global__ void k_decode_weights_nchw(const uint8_t* __restrict__ rows, const fl
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int ch = (i % 16) + 16 * ((i / 64) % (S / 16)), kq = (i / 16) % 4, step = i / (4 * S);
     const int k = 4 * step + kq;
-    float w = 0.0f;
-    if (ch < Ct && k < Cin * knl * knl) {
-      const int kw = k % knl, kh = (k / knl) % knl, c = k / (knl * knl);
-      const int slot = rows[(size_t)(kh * knl + kw) * sl.rowStride + qk_slot_entry(sl, 0, ch)];
-      w = ctrd[(size_t)c * K + qcnn_row_slot(slot)];
-    }
-    out[i] = w;
+    out[i] = ch < Ct && k < Cin * knl * knl ? code_word(rows, ctrd, sl, knl, K, k / (knl * knl), (k / knl) % knl, k % knl, ch) : 0.0f;
   }
 }
 
@@ -521,15 +576,16 @@ __global__ void k_decode_weights_nchw(const uint8_t* __restrict__ rows, const fl
 //     x3 w1, x2 w2, x1 w3, x2 w1, x1 w2, x1 w1      (in that order: small terms first),
 // go to v_mfma_f32_16x16x32_bf16 — each bf16 x bf16 product is exact in fp32, the accumulator is fp32 — while the dropped
 // x2 w3, x3 w2, x3 w3 are of order 2^-24, one fp32 rounding.  Six 16-cycle MFMAs per 32 k: 3 cycles per k against 8.
-// Layout: a lane (li, kg) of a 16x16x32 product holds row li (image li & 7, position li >> 3: the tile of the f32 kernel)
-// and k = 8 kg .. 8 kg + 7 of the step; k is flat over the window as above, padded to a multiple of 32 (the offset table
-// repeats the window's last element, the code words there are zero).  A step: 8 dword loads per image tile (same loads per
-// k as the f32 kernel), split once in registers and shared by the six channel tiles (36 MFMAs per fragment).  Code words:
-// the decoder writes the pieces once per upload; w1 and w2 stay in LDS (Kb x Ct x 4 bytes: 144 KB for AlexNet conv1 — all
-// three planes would be 216 KB), w3 (74 KB) streams from L2 through the buffer loads, one dwordx4 per channel tile and step.
-// Operand loads are inline assembly with counted waits (see the f32 kernel): step s splits its raw values, issues step
-// s + 1's loads into the same registers, then runs its channel tiles, each followed by the w3 load of step s + 1.  The
-// sum per output — bias, then per step the six terms in fixed order — depends on nothing but the output, as before.
+// Layout: a lane (li, kq) of a 16x16x32 product holds row li of the product tile (nchw_item) and k = 8 kq .. 8 kq + 7 of the
+// step; items, clamps (nchw_tile_bases) and stores (nchw_store) are the shared ones.  k is flat over the window as above,
+// padded to a multiple of 32 (the offset table repeats the window's last element, the code words there are zero).  A step:
+// 8 dword loads per image tile (same loads per k as the f32 kernel), split once in registers and shared by the six channel
+// tiles (36 MFMAs per fragment).  Code words: the decoder writes the pieces once per upload; w1 and w2 stay in LDS (Kb x Ct x
+// 4 bytes: 144 KB for AlexNet conv1 — all three planes would be 216 KB), w3 (74 KB) streams from L2 through the buffer loads,
+// one dwordx4 per channel tile and step.  Operand loads are inline assembly with counted waits (see the f32 kernel): step s
+// splits its raw values, issues step s + 1's loads into the same registers, then runs its channel tiles, each followed by
+// the w3 load of step s + 1.  The sum per output — bias, then per step the six terms in fixed order — depends on nothing but
+// the output, as before.
 // RUNS (the default where it fits, nchw_split_runs): k in RUN ORDER instead.  Every (channel, kernel row) of the window is
 // cut into nr = ceil(knl / 4) runs of 4 consecutive columns; run r of a row starts at column min(4 r, knl - 4), so that
 // the last run overlaps its predecessor instead of reaching past the row (knl 11: columns 0, 4, 7), and the code words of
@@ -584,84 +640,36 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
   extern __shared__ __attribute__((aligned(16))) float ldsW[];          // [steps][S / 16][piece 2][64 lanes][8 bf16], then int [Kp + 32]
                                                                         // (RUNS: int [Kp / 4 + 8], one per run)
   const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
-  const int P = p.Ho * p.Wo;
   const int steps = p.Kp >> 5;                                          // Kp: Cin knl^2 padded to a multiple of 32
   const int CTs = p.S >> 4;                                             // channel tiles of the layer
-  const uint32_t imgBytes = (uint32_t)p.Cin * p.H * p.W * 4u, planeBytes = (uint32_t)p.H * p.W * 4u, rowBytes = (uint32_t)p.W * 4u;
   int* ldsOff = reinterpret_cast<int*>(ldsW + (size_t)p.Kp * p.S);
-  {
-    const int wq = (p.Kp * p.S) >> 2;                                   // w1, w2: 4 bytes per code word
-    const f32x4* __restrict__ wsrc = reinterpret_cast<const f32x4*>(p.wdec);
-    f32x4* ldsW4 = reinterpret_cast<f32x4*>(ldsW);
-    for (int i = threadIdx.x; i < wq; i += 64 * NCHW_WAVES) ldsW4[i] = wsrc[i];
-    if constexpr (RUNS) {
-      const int nr = (p.knl + 3) >> 2, nRuns = p.Cin * p.knl * nr;
-      for (int i = threadIdx.x; i < (p.Kp >> 2) + 8; i += 64 * NCHW_WAVES) {
-        const int r = min(i, nRuns - 1);
-        const int kw = min(4 * (r % nr), p.knl - 4), kh = (r / nr) % p.knl, c = r / (nr * p.knl);
-        ldsOff[i] = (int)((uint32_t)c * planeBytes + (uint32_t)kh * rowBytes + (uint32_t)kw * 4u);
-      }
-    } else {
-      for (int i = threadIdx.x; i < p.Kp + 32; i += 64 * NCHW_WAVES) {
-        const int k = min(i, p.Kr - 1);
-        const int kw = k % p.knl, kh = (k / p.knl) % p.knl, c = k / (p.knl * p.knl);
-        ldsOff[i] = (int)((uint32_t)c * planeBytes + (uint32_t)kh * rowBytes + (uint32_t)kw * 4u);
-      }
+  lds_fill<64 * NCHW_WAVES>(ldsW, p.wdec, (p.Kp * p.S) >> 2);          // w1, w2: 4 bytes per code word
+  if constexpr (RUNS) {
+    const int nr = (p.knl + 3) >> 2, nRuns = p.Cin * p.knl * nr;
+    for (int i = threadIdx.x; i < (p.Kp >> 2) + 8; i += 64 * NCHW_WAVES) {
+      const int r = min(i, nRuns - 1);
+      ldsOff[i] = nchw_win_off(p, r / (nr * p.knl), (r / nr) % p.knl, min(4 * (r % nr), p.knl - 4));
     }
+  } else {
+    nchw_flat_offsets(p, ldsOff, p.Kp + 32);
   }
   __syncthreads();
-  const int tiles = (p.live + 15) / 16;
-  const int chunks = p.Ct / (16 * CT);
-  const int WoG = (p.Wo + IT - 1) / IT, PG = p.Ho * WoG;
-  const int nItems = p.panels * PG * tiles * chunks;
-  const unsigned long long total = (unsigned long long)p.nImages * imgBytes;
-  typedef int i32x4_t __attribute__((ext_vector_type(4)));
-  const unsigned long long srcA = reinterpret_cast<unsigned long long>(p.src);
-  const i32x4_t rsrc4 = {(int)(unsigned)srcA, (int)((unsigned)(srcA >> 32) & 0xffffu),
-                         (int)(total < 0xffffffffull ? (unsigned)total : 0xffffffffu), 0x00020000};
+  const NchwGrid g = nchw_grid<CT, IT>(p);
+  const i32x4_t rsrc4 = raw_rsrc(p.src, (unsigned long long)p.nImages * g.imgBytes);
   // w3: [steps][S / 16][64 lanes][8 bf16] behind w1 / w2; the step in the VECTOR offset, so that the range check turns the
   // last step's pre-load of "step `steps`" into zeros
-  const unsigned long long w3A = reinterpret_cast<unsigned long long>(p.wdec) + (size_t)p.Kp * p.S * 4;
-  const uint32_t w3Bytes = (uint32_t)p.Kp * p.S * 2u, w3Step = (uint32_t)p.S * 64u;
-  const i32x4_t rsrcW = {(int)(unsigned)w3A, (int)((unsigned)(w3A >> 32) & 0xffffu), (int)w3Bytes, 0x00020000};
-  const int xcd = blockIdx.x & 7, nX = gridDim.x < 8 ? gridDim.x : 8;
-  const int wgX = (gridDim.x - xcd + 7) >> 3;
-  const int itemBeg = (int)((long long)nItems * xcd / nX), itemEnd = (int)((long long)nItems * (xcd + 1) / nX);
-  const bool sparse = itemEnd - itemBeg <= wgX * NCHW_WAVES;
-  for (int item = itemBeg + (sparse ? wave * wgX + (int)(blockIdx.x >> 3) : (int)(blockIdx.x >> 3) * NCHW_WAVES + wave); item < itemEnd;
-       item += wgX * NCHW_WAVES) {
-    int laneI = lane;
-    asm volatile("" : "+v"(laneI));
-    const int li = laneI & 15, kg = laneI >> 4;
-    const int it = item % tiles, cc = (item / tiles) % chunks, pg = (item / (tiles * chunks)) % PG, panel = item / (chunks * tiles * PG);
-    const int orow = pg / WoG, ocol = (pg % WoG) * IT;
-    const int r0 = orow * p.stride, c0 = ocol * p.stride;
-    const uint32_t img0 = (uint32_t)(p.panel0 + panel) * PANEL + (uint32_t)it * 16u;
-    const bool edge = img0 + 16u >= (uint32_t)p.nImages;                // every address clamped inside the batch: see k_conv_dec_nchw
-    const int laneOff = (int)((uint32_t)(li & 7) * imgBytes + (uint32_t)((li >> 3) * p.stride) * 4u);
-    const uint32_t base0 = img0 * imgBytes + (uint32_t)(r0 * p.W + c0) * 4u;
+  const uint32_t w3Step = (uint32_t)p.S * 64u;
+  const i32x4_t rsrcW = raw_rsrc(p.wdec + (size_t)p.Kp * p.S, (uint32_t)p.Kp * p.S * 2u);
+  const ItemRange ir = xcd_items<NCHW_WAVES, true>(g.nItems, wave);
+  for (int item = ir.first; item < ir.end; item += ir.stride) {
+    const NchwItem w = nchw_item<IT>(p, g, item, lane);
    auto body = [&](auto edgeTag) {
-    constexpr bool EDGE = decltype(edgeTag)::value;
-    int laneOffE[IT];
-    uint32_t baseS[IT];
-#pragma unroll
-    for (int ti = 0; ti < IT; ++ti) {
-      laneOffE[ti] = laneOff;
-      baseS[ti] = base0 + (uint32_t)(ti & 1) * 8u * imgBytes + (uint32_t)((ti >> 1) * 2 * p.stride) * 4u;
-    }
-    if constexpr (EDGE) {
-      const uint32_t lastImg = (uint32_t)p.nImages - 1u, lastPos = (uint32_t)p.Wo - 1u;
-#pragma unroll
-      for (int ti = 0; ti < IT; ++ti) {
-        const uint32_t imgS = min(img0 + 8u * (uint32_t)(ti & 1), lastImg), imgL = min(img0 + 8u * (uint32_t)(ti & 1) + (uint32_t)(li & 7), lastImg);
-        const uint32_t posS = min((uint32_t)ocol + 2u * (uint32_t)(ti >> 1), lastPos), posL = min((uint32_t)ocol + 2u * (uint32_t)(ti >> 1) + (uint32_t)(li >> 3), lastPos);
-        laneOffE[ti] = (int)((imgL - imgS) * imgBytes + (posL - posS) * (uint32_t)p.stride * 4u);
-        baseS[ti] = imgS * imgBytes + ((uint32_t)(r0 * p.W) + posS * (uint32_t)p.stride) * 4u;
-      }
-    }
-    const int* __restrict__ offT = ldsOff + (RUNS ? 2 : 8) * kg;
+    int laneOffT[IT];
+    uint32_t baseT[IT];
+    nchw_tile_bases<decltype(edgeTag)::value>(p, g, w, laneOffT, baseT);
+    const int* __restrict__ offT = ldsOff + (RUNS ? 2 : 8) * w.kq;
     f32x4 xr[IT][2];                                                    // raw operands of the next step
-    // the operand loads of step s (lane: k = 32 s + 8 kg + j).  RUNS: 2 x IT, one dwordx4 per run (k = 4 run + e)
+    // the operand loads of step s (lane: k = 32 s + 8 kq + j).  RUNS: 2 x IT, one dwordx4 per run (k = 4 run + e)
     auto issue_x = [&, rsrc4](int s) {
       if constexpr (RUNS) {
         typedef int i32x2_t __attribute__((ext_vector_type(2)));
@@ -675,7 +683,7 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
               asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(o[h]));
               xr[ti][h] = f32x4{v, v, v, v};
             } else
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(xr[ti][h]) : "v"(o[h] + laneOffE[ti]), "s"(rsrc4), "s"(baseS[ti]));
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(xr[ti][h]) : "v"(o[h] + laneOffT[ti]), "s"(rsrc4), "s"(baseT[ti]));
           }
         return;
       }
@@ -687,7 +695,7 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
         for (int j = 0; j < 8; ++j) {
           float v;
           if (NCHW_VAR & 1) asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(ot[j]));
-          else asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(ot[j] + laneOffE[ti]), "s"(rsrc4), "s"(baseS[ti]));
+          else asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(ot[j] + laneOffT[ti]), "s"(rsrc4), "s"(baseT[ti]));
           xr[ti][j >> 2][j & 3] = v;
         }
     };
@@ -696,17 +704,12 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
     auto issue_w3 = [&, rsrcW, w3Step](int s, int ct) {
       if (NCHW_VAR & 16) asm volatile("v_mov_b32 %0, %1" : "=v"(w3[ct][0]) : "v"(s)); else
       asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(w3[ct]) : "v"(w3Lane + (int)(s * w3Step)), "s"(rsrcW),
-                   "s"((uint32_t)((cc * CT + ct) * 1024)));
+                   "s"((uint32_t)((w.cc * CT + ct) * 1024)));
     };
     f32x4 acc[CT][IT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const float b1 = p.bias[(cc * CT + ct) * 16 + li];
-#pragma unroll
-      for (int ti = 0; ti < IT; ++ti) acc[ct][ti] = f32x4{b1, b1, b1, b1};
-    }
+    nchw_bias(p, w, acc);
     // w1 / w2 of (step, channel tile) in LDS: 1 KB per piece, lane-contiguous 16-byte reads
-    const u32x4* __restrict__ wl = reinterpret_cast<const u32x4*>(ldsW) + (size_t)(cc * CT) * 128 + lane;
+    const u32x4* __restrict__ wl = reinterpret_cast<const u32x4*>(ldsW) + (size_t)(w.cc * CT) * 128 + lane;
     const int wStep = CTs * 128;                                        // u32x4 per step
     issue_x(0);
 #pragma unroll
@@ -754,37 +757,9 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
     split_wait<0>(xr);                                                  // nothing in flight into registers the stores may reuse
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) split_wait<0>(w3[ct]);
-    {
-      const int nPos = (NCHW_VAR & 4) ? (p.Wo < 0 ? IT : 0) : min(IT, p.Wo - ocol);
-      float* __restrict__ dst = p.dst + (((size_t)panel * P + orow * p.Wo + ocol + (kg >> 1)) * p.Ct + li) * PANEL + it * 16 + 4 * (kg & 1);
-      if (p.relu) {
-#pragma unroll
-        for (int tp = 0; tp < IT / 2; ++tp)
-          if (tp * 2 + (kg >> 1) < nPos) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-              for (int h = 0; h < 2; ++h) {
-                const int ti = tp * 2 + h;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = (0.0f < acc[ct][ti][e]) ? acc[ct][ti][e] : 0.0f;
-                *reinterpret_cast<f32x4*>(dst + ((size_t)tp * 2 * p.Ct + (cc * CT + ct) * 16) * PANEL + 8 * h) = v;
-                __builtin_amdgcn_sched_barrier(0);
-              }
-          }
-      } else {
-#pragma unroll
-        for (int ti = 0; ti < IT; ++ti)
-          if ((ti >> 1) * 2 + (kg >> 1) < nPos) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-              *reinterpret_cast<f32x4*>(dst + ((size_t)(ti >> 1) * 2 * p.Ct + (cc * CT + ct) * 16) * PANEL + 8 * (ti & 1)) = acc[ct][ti];
-          }
-      }
-    }
+    nchw_store(p, w, acc);
    };
-    if (edge) body(std::true_type{}); else body(std::false_type{});
+    if (w.edge) body(std::true_type{}); else body(std::false_type{});
   }
 }
 
@@ -814,10 +789,7 @@ __global__ void k_decode_weights_split(const uint8_t* __restrict__ rows, const f
       kw = min(4 * ri, knl - 4) + (k & 3); kh = (r / nr) % knl; c = r / (nr * knl);
       live = r < Cin * knl * nr && kw >= 4 * ri;
     }
-    if (ch < Ct && live) {
-      const int slot = rows[(size_t)(kh * knl + kw) * sl.rowStride + qk_slot_entry(sl, 0, ch)];
-      w = ctrd[(size_t)c * K + qcnn_row_slot(slot)];
-    }
+    if (ch < Ct && live) w = code_word(rows, ctrd, sl, knl, K, c, kh, kw, ch);
     uint16_t h1, h2, h3;
     const float r = w - bf16_hi(w, &h1);
     (void)bf16_hi(r - bf16_hi(r, &h2), &h3);
@@ -1020,18 +992,14 @@ hipError_t qk_fc_dec(const FcDecParams& p, int slices, int live, hipStream_t st)
   FcDecParams q = p;
   q.halves = (live + 63) / 64;
   const dim3 grid((unsigned)((p.Ct + 63) / 64), (unsigned)(p.panels * q.halves), (unsigned)slices);
-  const size_t shm = 8 * 16 * 256 * sizeof(float);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fc_dec), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_fc_dec, grid, dim3(1024), shm, st, q);
-  return hipGetLastError();
+  return launch_lds(k_fc_dec, grid, dim3(1024), 8 * 16 * 256 * sizeof(float), st, q);
 }
 
-bool qk_conv_dec_nchw_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kp, int* S) {
+bool qk_conv_dec_nchw_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kp) {
   if (grp != 1 || M != 1 || Cin < 1 || Cin > 4 || pad != 0 || Ct % 96) return false;
   const int kp = (Cin * knl * knl + 15) / 16 * 16;            // steps in fours
   if ((size_t)(kp + 4) * Ct * sizeof(float) + (kp / 4 + 4) * 16 > 160 * 1024) return false;   // code words + one step of slack + offset table
-  *Kp = kp; *S = Ct;
+  *Kp = kp;
   return true;
 }
 
@@ -1042,23 +1010,23 @@ hipError_t qk_decode_weights_nchw(const uint8_t* rows, const float* ctrd, float*
   return hipGetLastError();
 }
 
-// p.Kr = Cin knl^2, p.Kp = qk_conv_dec_nchw_shape's, p.S = Ct
-hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st) {
+// The checks of both NCHW kernels' launches (an NCHW batch whose byte offsets fit 32 bits, an unpadded layer, 96-channel
+// chunks, S = Ct) and their grid: one persistent workgroup per CU, fewer for few items (one each, see xcd_items)
+static hipError_t launch_nchw(void (*kern)(DecParams), size_t shm, const DecParams& p, hipStream_t st) {
   if (!p.srcNchw || p.pad != 0 || p.Ct % 96 || p.S != p.Ct || (unsigned long long)p.nImages * p.Cin * p.H * p.W * 4ull >= (1ull << 32))
     return hipErrorInvalidValue;
   const long long items = (long long)p.panels * p.Ho * ((p.Wo + 3) / 4) * ((p.live + 15) / 16) * (p.Ct / 96);
-  const int blocks = (int)std::min<long long>(256, items);           // (few items: one per workgroup, see `sparse`)
-  const size_t shm = (size_t)(p.Kp + 4) * p.S * sizeof(float) + (size_t)(p.Kp / 4 + 4) * 16;
-  auto kern = k_conv_dec_nchw<6, 4>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NCHW_WAVES), shm, st, p);
-  return hipGetLastError();
+  return launch_lds(kern, dim3((int)std::min<long long>(256, items)), dim3(64 * NCHW_WAVES), shm, st, p);
+}
+
+// p.Kr = Cin knl^2, p.Kp = qk_conv_dec_nchw_shape's, p.S = Ct
+hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st) {
+  return launch_nchw(k_conv_dec_nchw<6, 4>, (size_t)(p.Kp + 4) * p.S * sizeof(float) + (size_t)(p.Kp / 4 + 4) * 16, p, st);
 }
 
 bool qk_conv_dec_nchw_split_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kb) {
-  int kp = 0, s = 0;
-  if (!qk_conv_dec_nchw_shape(Cin, grp, M, Ct, knl, pad, &kp, &s)) return false;
+  int kp = 0;
+  if (!qk_conv_dec_nchw_shape(Cin, grp, M, Ct, knl, pad, &kp)) return false;
   const int nr = nchw_split_runs(Cin, knl, Ct);               // run order where it fits, else flat
   const int kb = nchw_split_kb(Cin, knl, nr);                 // steps of 32 k
   if (nchw_split_lds(kb, Ct, nr) > 160 * 1024) return false;  // w1 / w2 + offset table
@@ -1078,15 +1046,6 @@ hipError_t qk_decode_weights_split(const uint8_t* rows, const float* ctrd, uint1
 // p.Kr = Cin knl^2, p.Kp = qk_conv_dec_nchw_split_shape's Kb, p.S = Ct, p.wdec = qk_decode_weights_split's planes
 hipError_t qk_conv_dec_nchw_split(const DecParams& p, hipStream_t st) {
   const int nr = nchw_split_runs(p.Cin, p.knl, p.Ct);         // the order qk_decode_weights_split wrote
-  if (!p.srcNchw || p.pad != 0 || p.Ct % 96 || p.S != p.Ct || p.Kp != nchw_split_kb(p.Cin, p.knl, nr) ||
-      (unsigned long long)p.nImages * p.Cin * p.H * p.W * 4ull >= (1ull << 32))
-    return hipErrorInvalidValue;
-  const long long items = (long long)p.panels * p.Ho * ((p.Wo + 3) / 4) * ((p.live + 15) / 16) * (p.Ct / 96);
-  const int blocks = (int)std::min<long long>(256, items);
-  const size_t shm = nchw_split_lds(p.Kp, p.S, nr);
-  auto kern = nr ? k_conv_dec_nchw_split<6, 4, true> : k_conv_dec_nchw_split<6, 4, false>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NCHW_WAVES), shm, st, p);
-  return hipGetLastError();
+  if (p.Kp != nchw_split_kb(p.Cin, p.knl, nr)) return hipErrorInvalidValue;
+  return launch_nchw(nr ? k_conv_dec_nchw_split<6, 4, true> : k_conv_dec_nchw_split<6, 4, false>, nchw_split_lds(p.Kp, p.S, nr), p, st);
 }

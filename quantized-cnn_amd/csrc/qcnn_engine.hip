@@ -249,17 +249,13 @@ int plan_arena(QcnnCtx* c) {
     s.hasDmap = (d.type == QCNN_FCNT && l == c->firstFc && c->dims[l].h * c->dims[l].w > 1);
     if (d.type == QCNN_CONV && qk_conv_dec_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, &s.decKp, &s.decS)) {
       s.offDec = off; off = align_up(off + sizeof(float) * (size_t)d.knlSiz * s.decKp * s.decS, 256);
-      int nS = 0;
       s.decNV = 0;
-      if (l == 0 && qk_conv_dec_nchw_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, d.padSiz, &s.decNV, &nS)) {
-        s.offDecN = off; off = align_up(off + sizeof(float) * (size_t)s.decNV * nS, 256);
-        s.decBK = 0;
+      s.decBK = 0;
+      if (l == 0 && qk_conv_dec_nchw_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, d.padSiz, &s.decNV)) {
+        s.offDecN = off; off = align_up(off + sizeof(float) * (size_t)s.decNV * Ct, 256);
         if (qk_conv_dec_nchw_split_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, d.padSiz, &s.decBK)) {   // derived like the copy above
           s.offDecB = off; off = align_up(off + 6 * (size_t)s.decBK * Ct, 256);                           // w1, w2, w3: 2 bytes each
         }
-      } else {
-        s.decNV = 0;
-        s.decBK = 0;
       }
     } else if (d.type == QCNN_FCNT && !s.hasDmap && qk_fc_dec_shape((int)fm_elems(c, l), s.M, s.Cs, Ct, &s.decS)) {
       s.decKp = -1;                   // FC layer with one-dim sub-spaces: [D][decS] decoded code words

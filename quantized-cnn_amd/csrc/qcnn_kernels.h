@@ -388,11 +388,11 @@ hipError_t qk_decode_weights(const uint8_t* rows, const float* ctrd, float* out,
                              int Ct, int Kp, int S, hipStream_t st);
 hipError_t qk_conv_dec(const DecParams& p, hipStream_t st);
 // The same layer reading the NCHW network input in place (no pack pass), k flat over the window (Cin knl^2 products in
-// fours, padded to Kp = a multiple of 16): unpadded layers.  wdec: [Kp / 4 steps][S / 16][4 k][16], S = Ct.
-bool qk_conv_dec_nchw_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kp, int* S);
+// fours, padded to Kp = a multiple of 16): unpadded layers.  wdec: [Kp / 4 steps][Ct / 16][4 k][16] (channel stride S = Ct).
+bool qk_conv_dec_nchw_shape(int Cin, int grp, int M, int Ct, int knl, int pad, int* Kp);
 hipError_t qk_decode_weights_nchw(const uint8_t* rows, const float* ctrd, float* out, const QkSlots& sl, int knl, int Cin, int K,
                                   int Ct, int Kp, int S, hipStream_t st);
-hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st);   // p.Kr = Cin knl^2, p.Kp and p.S from qk_conv_dec_nchw_shape
+hipError_t qk_conv_dec_nchw(const DecParams& p, hipStream_t st);   // p.Kr = Cin knl^2, p.Kp from qk_conv_dec_nchw_shape, p.S = Ct
 // Its fp32-accurate split-bf16 form (QCNN_OPT_DEC_BF16SPLIT): k padded to Kb = a multiple of 32; wdec = the code words split
 // into three bf16 pieces, w1 / w2 [Kb / 32][Ct / 16][2][64][8] then w3 [Kb / 32][Ct / 16][64][8] (Kb x Ct x 6 bytes).  k is
 // in run order (runs of 4 columns of a kernel row, read with 16-byte loads) where that fits LDS and knl >= 4, else flat over
