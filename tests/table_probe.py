@@ -1,0 +1,280 @@
+"""TEST HELPER — one-hot assignment probes: read single look-up-table entries out of a conv / FC layer, exactly.
+
+A conv / FC output is ``bias + sum over (kh, kw, m) of T[pixel][m][asmt[ct][kh][kw][m]]`` (src/CaffeEva.cc:760-868, 968-1025).
+With ``bias = 0``, one all-zero code word per sub-space (the *silent* word: its table entry is exactly 0.0f under any builder)
+and assignments that name the silent word everywhere except at ONE (kh*, kw*, m*) per output channel, where they name k*,
+
+    out[n, ho, wo, ct] = 0 + ... + T[n, (ho*s - pad + kh*, wo*s - pad + kw*), m*, k*] + ... + 0
+
+and adding 0.0f is exact in any order, grouping or accumulator layout: the output IS the table entry (or exactly 0 where
+the tap lies in the padding, which the reference skips).  So an entry can be held to the textbook bound of an fp32 dot
+product against a float64 one, per entry and relative to the entry's own magnitude:
+
+    |T - T64| <= gamma_n * sum_j |x_j c_j|,   gamma_n = n u / (1 - n u),   u = 2^-24,   n = CsEff
+
+(n rounded products, n - 1 rounded additions behind the exact 0 + p_0; an f32 MFMA is a k-ordered fmaf chain, one rounding
+per step).  The exact builder must moreover return the float32 sequence ``acc = acc + x_j * c_j`` bit for bit.
+
+Plain numpy; no GPU, no oracle.  Layouts are the reference's file layouts, as synth.make_params writes them: ctrd [M][K][Cs]
+(dims >= CsEff of a partial last sub-space zero), asmt 0-based uint8 [Ct][kh][kw][M] (conv) / [Ct][M] (FC).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+U = 2.0 ** -24                     # unit round-off of float32
+LO, HI = 2.0 ** -60, 2.0 ** 60     # every |x_j c_j| of a probe stays inside: no subnormals, no overflow
+
+
+def gamma(n):
+    return n * U / (1.0 - n * U)
+
+
+SPLIT_BF16_PRODUCT = 2.0 ** -22    # three bf16 pieces per operand, six cross terms: each product within 2^-22 (test_bf16split_cpu.py)
+
+
+def split_extra(cs_eff):
+    """What the split-bf16 decoded conv may add to gamma_CsEff: `check(.., n_terms=cs_eff, extra=split_extra(cs_eff))` is the
+    bound (2^-22 + gamma_(6 CsEff)) * mag — six cross terms per product, at most 6 CsEff fp32 additions."""
+    return SPLIT_BF16_PRODUCT + gamma(6 * cs_eff) - gamma(cs_eff)
+
+
+# ---------------------------------------------------------------- geometry ----
+def conv_geom(H, W, Cin, knl, stride, pad, grp, Ct):
+    return dict(H=H, W=W, Cin=Cin, knl=knl, stride=stride, pad=pad, grp=grp, Ct=Ct)
+
+
+def fc_geom(D, Ct):
+    return dict(D=D, Ct=Ct)
+
+
+def _dims(kind, g):
+    """(Ct, taps per side, input dims one group's code book spans)."""
+    if kind == "conv":
+        return g["Ct"], g["knl"], g["Cin"] // g["grp"]
+    return g["Ct"], 1, g["D"]
+
+
+def cs_eff(kind, g, M, Cs):
+    _, _, d = _dims(kind, g)
+    assert (M - 1) * Cs < d <= M * Cs, (d, M, Cs)
+    return [min(d - m * Cs, Cs) for m in range(M)]
+
+
+def out_hw(g):
+    return ((g["H"] + 2 * g["pad"] - g["knl"]) // g["stride"] + 1, (g["W"] + 2 * g["pad"] - g["knl"]) // g["stride"] + 1)
+
+
+# ---------------------------------------------------------------- schedule ----
+def schedule(kind, g, M, K, Cs, max_rounds=None, negate=False):
+    """The rounds of a probe: a list of dict(r, silent, negate).  Round r names, for channel ct, pair number
+    q = r * Ct + ct of the (m, k) enumeration below and tap q mod knl^2, so that ceil(M (K - 1) / Ct) rounds name every
+    (m, k >= 1) and ceil(knl^2 / Ct) rounds every tap, corners included.  The rounds after those use code word K - 1 as the
+    silent one and start the enumeration at k = 0 (ceil(M / Ct) rounds name k = 0 in every sub-space).  max_rounds thins the
+    first kind (the caller states the share covered); negate adds every round once more with the code book negated (fused
+    ReLU: both signs are seen)."""
+    Ct, knl, _ = _dims(kind, g)
+    n_main = max(-(-M * (K - 1) // Ct), -(-knl * knl // Ct))
+    if max_rounds is not None:
+        n_main = min(n_main, max_rounds)
+    n_sil = -(-M // Ct)
+    rounds = [dict(r=r, silent=0, negate=False) for r in range(n_main)]
+    rounds += [dict(r=r, silent=K - 1, negate=False) for r in range(n_sil)]
+    if negate:
+        rounds += [dict(rd, negate=True) for rd in rounds]
+    return rounds
+
+
+def picks_of_round(kind, g, M, K, rd):
+    """Per channel (kh*, kw*, m*, k*) [Ct, 4] of a round.  Pair q -> m = q mod M, k from q div M: neighbouring channels
+    (lanes) differ in sub-space and in code word."""
+    Ct, knl, _ = _dims(kind, g)
+    q = rd["r"] * Ct + np.arange(Ct)
+    m = q % M
+    if rd["silent"] == 0:                              # silent word 0: k in 1 .. K-1, shifted by m so that one round of a
+        k = (q // M + m) % (K - 1) + 1                 # thinned schedule already names every k (a bijection for every m)
+    else:                                              # silent word K-1: k in 0 .. K-2, k = 0 first in every sub-space
+        k = (q // M) % (K - 1)
+    t = q % (knl * knl)
+    return np.stack([t // knl, t % knl, m, k], axis=1).astype(np.int64)
+
+
+def probe_params(kind, g, M, K, Cs, rd, seed=0):
+    """dict(bias, ctrd, asmt, bits, picks) of round rd: the file layout of synth.make_params.  Code words: standard normal
+    float32 (full mantissas), magnitudes kept >= 2^-6; the silent word and the dims >= CsEff are zero."""
+    Ct, knl, _ = _dims(kind, g)
+    cse = cs_eff(kind, g, M, Cs)
+    rng = np.random.default_rng([seed, 17])            # the same code book in every round of a case
+    ctrd = _away_from_zero(rng.standard_normal((M, K, Cs)).astype(np.float32))
+    for m in range(M):
+        ctrd[m, :, cse[m]:] = 0.0
+    ctrd[:, rd["silent"], :] = 0.0
+    if rd["negate"]:
+        ctrd = -ctrd
+    picks = picks_of_round(kind, g, M, K, rd)
+    ct = np.arange(Ct)
+    if kind == "conv":
+        asmt = np.full((Ct, knl, knl, M), rd["silent"], np.uint8)
+        asmt[ct, picks[:, 0], picks[:, 1], picks[:, 2]] = picks[:, 3]
+    else:
+        asmt = np.full((Ct, M), rd["silent"], np.uint8)
+        asmt[ct, picks[:, 2]] = picks[:, 3]
+    bits = max(1, int(K - 1).bit_length())
+    return dict(bias=np.zeros(Ct, np.float32), ctrd=ctrd, asmt=asmt, bits=bits, picks=picks)
+
+
+def _away_from_zero(v, floor=2.0 ** -6):
+    v = np.asarray(v, np.float32)
+    return np.where(np.abs(v) < floor, v + np.copysign(np.float32(floor), v), v).astype(np.float32)
+
+
+def activations(kind, g, n, seed, scaled):
+    """Input of the probed layer: NHWC [n, H, W, Cin] (conv) / [n, D] (FC), float32 standard normal with full mantissas
+    (magnitudes >= 2^-6); scaled: times 2^e per image and per channel, e uniform in -20 .. 20 (an absolute instead of a
+    relative error of a builder shows only there)."""
+    rng = np.random.default_rng([seed, 29, int(scaled)])
+    shape = (n, g["H"], g["W"], g["Cin"]) if kind == "conv" else (n, g["D"])
+    x = _away_from_zero(rng.standard_normal(shape).astype(np.float32))
+    if scaled:
+        e = rng.integers(-20, 21, size=(n, shape[-1]))
+        x = x * np.exp2(e).astype(np.float32).reshape((n,) + (1,) * (len(shape) - 2) + (shape[-1],))
+    return np.ascontiguousarray(x, np.float32)
+
+
+# ---------------------------------------------------------------- expected entries ----
+def expected(kind, g, x, params, block=64):
+    """(want64, mag, want32_seq) of the probe `params` on input x (layout of `activations`), shaped like the layer's output
+    [n, Ho, Wo, Ct] (FC: [n, Ct]): the float64 entry, sum_j |x_j c_j| in float64, and the float32 sequence
+    acc = 0; acc = acc + x_j * c_j (j ascending over CsEff).  Where the tap lies in the padding all three are 0.
+    Groups: channel ct of group g reads input channels g * Cg + m* Cs + j, the same code book in every group."""
+    x = np.asarray(x, np.float32)
+    ctrd, picks = params["ctrd"], params["picks"]
+    M, K, Cs = ctrd.shape
+    Ct = picks.shape[0]
+    cse = np.array(cs_eff(kind, g, M, Cs))
+    words = ctrd[picks[:, 2], picks[:, 3]]                                     # [Ct, Cs], zero beyond CsEff
+    live = np.arange(Cs)[None, :] < cse[picks[:, 2]][:, None]                   # [Ct, Cs]
+    if kind == "fc":
+        idx = np.minimum(picks[:, 2:3] * Cs + np.arange(Cs)[None, :], g["D"] - 1)
+        want64, mag, seq = _dot(np.where(live[None], x[:, idx], np.float32(0)), words[None])
+        return want64, mag, seq
+    n, H, W, Cin = x.shape
+    knl, s, pad, grp = g["knl"], g["stride"], g["pad"], g["grp"]
+    Ho, Wo = out_hw(g)
+    Cg, Ctg = Cin // grp, Ct // grp
+    xp = np.zeros((n, H + 2 * pad, W + 2 * pad, Cin), np.float32)               # zero padding: products there are exact zeros
+    xp[:, pad:pad + H, pad:pad + W] = x
+    want64 = np.zeros((n, Ho, Wo, Ct), np.float64)
+    mag = np.zeros((n, Ho, Wo, Ct), np.float64)
+    seq = np.zeros((n, Ho, Wo, Ct), np.float32)
+    for ct in range(Ct):
+        kh, kw, m, _ = picks[ct]
+        c0 = (ct // Ctg) * Cg + m * Cs
+        sl = xp[:, kh:kh + (Ho - 1) * s + 1:s, kw:kw + (Wo - 1) * s + 1:s, c0:c0 + cse[m]]
+        want64[..., ct], mag[..., ct], seq[..., ct] = _dot(sl, words[ct, :cse[m]])
+        inside_h = (np.arange(Ho) * s - pad + kh >= 0) & (np.arange(Ho) * s - pad + kh < H)
+        inside_w = (np.arange(Wo) * s - pad + kw >= 0) & (np.arange(Wo) * s - pad + kw < W)
+        assert ((mag[0, :, :, ct] > 0) == (inside_h[:, None] & inside_w[None, :])).all()
+    return want64, mag, seq
+
+
+def _dot(xs, cs):
+    """xs [..., J] float32, cs broadcastable [..., J] float32 -> float64 dot, float64 sum of |products|, float32 sequence."""
+    xs, cs = np.asarray(xs, np.float32), np.asarray(cs, np.float32)
+    p64 = xs.astype(np.float64) * cs.astype(np.float64)
+    a = np.abs(p64)
+    nz = a[a > 0]
+    assert nz.size == 0 or (nz.min() >= LO and nz.max() <= HI), "probe products outside [2^-60, 2^60]"
+    acc = np.zeros(np.broadcast(xs, cs).shape[:-1], np.float32)
+    for j in range(xs.shape[-1]):
+        acc = acc + xs[..., j] * cs[..., j]                                     # numpy: one rounding per operation, no FMA
+    return p64.sum(-1), a.sum(-1), acc
+
+
+# ---------------------------------------------------------------- the checker ----
+def check(y, want64, mag, n_terms, extra=0.0, relu=False, what=""):
+    """Assert |y - want64| <= (gamma_n + extra) * mag for every element (n_terms = 1: one rounding, u * mag), exact zeros
+    where mag = 0; relu: y is max(entry, 0) (the clamp does not increase the distance to max(want64, 0)).  Returns the
+    worst err / bound over the informative elements (mag > 0)."""
+    y = np.asarray(y)
+    assert y.shape == want64.shape == mag.shape, (y.shape, want64.shape, mag.shape)
+    assert np.isfinite(y).all(), "%s: non-finite output" % what
+    w = np.maximum(want64, 0.0) if relu else want64
+    err = np.abs(y.astype(np.float64) - w)
+    bound = ((U if n_terms == 1 else gamma(n_terms)) + extra) * mag
+    dead = mag == 0
+    assert not (dead & (y != 0)).any(), "%s: %d non-zero outputs where the tap lies in the padding" % (what, int((dead & (y != 0)).sum()))
+    bad = err > bound
+    if bad.any():
+        i = np.unravel_index(np.argmax(np.where(dead, 0.0, err / np.where(dead, 1.0, bound))), err.shape)
+        raise AssertionError("%s: %d of %d entries beyond the bound; worst at %r: got %.9g want %.17g err %.3g bound %.3g"
+                             % (what, int(bad.sum()), err.size, i, float(y[i]), float(w[i]), float(err[i]), float(bound[i])))
+    return float((err[~dead] / bound[~dead]).max()) if (~dead).any() else 0.0
+
+
+def informative_share(mag):
+    return float((mag > 0).mean())
+
+
+def covered(kind, g, M, K, rounds):
+    """(pairs [M, K] bool: (m, k) named by some round as a non-silent word; taps [knl, knl] bool; pairs_inside [M, K] bool:
+    named at least once with a tap that lies inside the map for some output position)."""
+    _, knl, _ = _dims(kind, g)
+    pairs = np.zeros((M, K), bool)
+    inside = np.zeros((M, K), bool)
+    taps = np.zeros((knl, knl), bool)
+    for rd in rounds:
+        p = picks_of_round(kind, g, M, K, rd)
+        pairs[p[:, 2], p[:, 3]] = True
+        taps[p[:, 0], p[:, 1]] = True
+        if kind == "conv":
+            Ho, Wo = out_hw(g)
+            ok = np.array([_tap_inside(g, kh, g["H"], Ho) and _tap_inside(g, kw, g["W"], Wo) for kh, kw in p[:, :2]])
+        else:
+            ok = np.ones(len(p), bool)
+        inside[p[ok, 2], p[ok, 3]] = True
+    return pairs, taps, inside
+
+
+def _tap_inside(g, k, size, n_out):
+    pos = np.arange(n_out) * g["stride"] - g["pad"] + k
+    return bool(((pos >= 0) & (pos < size)).any())
+
+
+# ---------------------------------------------------------------- the shapes the probes run on ----
+# name -> (kind, geometry, M, K, Cs, max_rounds).  tests/test_table_probe_cpu.py pins the helper to the oracle on every one of
+# them and checks the schedules' coverage; tests/test_gpu_table_probe.py sends them through the kernel families.
+SHAPES = {
+    # AlexNet conv2: 2 groups x 128 channels, 5x5 / 1, pad 2, six sub-spaces of 8 dims, on a 13x13 map
+    "alex_conv2": ("conv", conv_geom(13, 13, 96, 5, 1, 2, 2, 256), 6, 128, 8, None),
+    "c3_64": ("conv", conv_geom(13, 13, 16, 3, 1, 1, 1, 64), 2, 128, 8, None),
+    "c3_128": ("conv", conv_geom(13, 13, 16, 3, 1, 1, 1, 128), 2, 128, 8, None),
+    "partial": ("conv", conv_geom(11, 11, 20, 3, 1, 1, 1, 64), 3, 128, 8, None),          # last sub-space: 4 of 8 dims
+    "cs4_2x2": ("conv", conv_geom(11, 11, 16, 2, 1, 0, 1, 128), 4, 128, 4, None),
+    "rgb7": ("conv", conv_geom(31, 31, 3, 7, 2, 0, 1, 32), 1, 128, 8, None),              # one 3-dim sub-space
+    "s5x5_2": ("conv", conv_geom(21, 21, 16, 5, 2, 2, 1, 96), 2, 128, 8, None),
+    "c192": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 192), 2, 128, 8, None),
+    "c256": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 256), 2, 128, 8, None),
+    "c384": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 384), 2, 128, 8, None),
+    "c512": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 512), 2, 128, 8, None),
+    "c256_cs4": ("conv", conv_geom(7, 7, 8, 3, 1, 1, 1, 256), 2, 128, 4, None),
+    "k10": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 64), 2, 10, 8, None),
+    "k64": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 64), 2, 64, 8, None),
+    "k200": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 64), 2, 200, 8, None),
+    "k256": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 64), 2, 256, 8, None),
+    # decoded first layers: AlexNet conv1 on a 67x71 input, four input channels, one input channel
+    "alex_conv1": ("conv", conv_geom(67, 71, 3, 11, 4, 0, 1, 96), 1, 128, 8, None),
+    "dec4": ("conv", conv_geom(28, 30, 4, 4, 2, 0, 1, 192), 1, 128, 4, None),
+    "dec1": ("conv", conv_geom(15, 17, 1, 3, 1, 0, 1, 96), 1, 128, 8, None),
+    # FC: 31 x 128 pairs over 768 channels (six rounds); AlexNet fc6 in ONE thinned round (4096 of 2304 x 31 pairs, every m,
+    # every k); a 200-channel layer; a classifier with 16 code words of one dim
+    "fc512": ("fc", fc_geom(512, 768), 128, 32, 4, None),
+    "fc6": ("fc", fc_geom(9216, 4096), 2304, 32, 4, 1),
+    "fc200": ("fc", fc_geom(256, 200), 64, 32, 4, None),
+    "fc_k16": ("fc", fc_geom(256, 1000), 256, 16, 1, None),
+}
+
+
+def shape_rounds(name, negate=False):
+    kind, g, M, K, Cs, mr = SHAPES[name]
+    return schedule(kind, g, M, K, Cs, max_rounds=mr, negate=negate)
