@@ -30,6 +30,9 @@
  *   / _set_layer_weights        -> CalcFeatMap_ConvPrec / _FCntPrec        src/CaffeEva.cc:681-758, 932-966
  *   qcnn_quantize_layer         produces what CaffePara::LoadLayerPara reads src/CaffePara.cc:262-288
  *                               (sub-codebooks + assignments) from the dense weights of :290-302
+ *   qcnn_calib_gram             (no counterpart: the reference ships finished parameters) second moments of a layer's
+ *   / qcnn_quantize_layer_ec    input windows — the windows CalcFeatMap_ConvAprx walks, src/CaffeEva.cc:787-827 — and the
+ *                               error-corrected quantisation of Wu et al., CVPR'16, sections 3.2 - 3.3, on them
  *   qcnn_run_layer              CaffeEva::CalcFeatMap on one layer         src/CaffeEva.cc:625-670
  *   qcnn_get_layer_output       featMapLst[l] read-back (parity dumps)     include/CaffeEva.h:109
  *   qcnn_get_layer_ms           swIndvLayerLst / DispElpsTime              src/CaffeEva.cc:297-326
@@ -46,7 +49,7 @@
 extern "C" {
 #endif
 
-#define QCNN_ABI_VERSION 5   /* 5 (round 6): QCNN_OPT_HALF8 (half-panel eight-wave workgroups), qcnn_model_arena_checksum / qcnn_group_arena_checksum,
+#define QCNN_ABI_VERSION 5   /* qcnn_calib_gram / qcnn_quantize_layer_ec are additive: the version stays 5.  5 (round 6): QCNN_OPT_HALF8 (half-panel eight-wave workgroups), qcnn_model_arena_checksum / qcnn_group_arena_checksum,
                               * qcnn_model_mark_loaded drops the lazily built fp16 program tables.  4 (round 5): QCNN_OPT_LUT_MODE 2 = fp16 table storage, 3 = fp16 tables + fp16 sums (the bf16-pair builder
                               * of version 3 is gone); qcnn_set_option rejects out-of-range values of QCNN_OPT_SYM / _SLIDE / _SYM8;
                               * qcnn_model_set_layer_shape accepts up to 256 code words per sub-space; qcnn_group_forward */
@@ -211,6 +214,41 @@ int qcnn_model_set_layer_weights(QcnnCtx* ctx, int layer, const float* bias, con
 int qcnn_quantize_layer(QcnnCtx* ctx, int Ct, int Cin, int kh, int kw, int M, int K, int Cs, const float* weights_host,
                         const float* ctrd_init_host, int max_iter, float* ctrd_out_host, uint8_t* asmt_out_host, double* sse2,
                         int* iters2);
+/* Error-corrected quantisation (Wu et al., "Quantized Convolutional Neural Networks for Mobile Devices", CVPR'16, sections
+ * 3.2 - 3.3; DESIGN.md "Error-corrected quantisation"): code books and assignments that minimise the error of the layer's
+ * RESPONSE on calibration inputs, J = sum_ct e_ct^T G_g(ct) e_ct with e_ct = w_ct - w_hat_ct in patch order
+ * p = (y*kw + x)*Cg + c and G_g = sum over calibration patches s of s s^T — instead of the error of the weights.
+ *
+ * qcnn_calib_gram: the raw fp64 sums G_g[p][q] = sum_images sum_output pixels s_p s_q of a layer's input windows (out-of-image
+ * taps are zeros).  in_nhwc_host = fm[layer] of n images, NHWC per image: what qcnn_run_layer takes and qcnn_get_layer_output
+ * returns (FC: H = W = 1, Cin_total = D, kh = kw = 1).  gram_inout_host [grp][P][P], P = kh*kw*Cin_total/grp; accumulate != 0
+ * adds to what it holds (calibration sets larger than one upload).  Products run on the matrix pipe in fp32 over runs of 256
+ * patches and in fp64 across runs: every entry within gamma_260 * sum |s_p s_q| of its exact value however large the set; the
+ * result is symmetric to the bit and the same bits from run to run.  Blocking; scratch is allocated per call and freed before
+ * return; works with or without a model loaded and changes nothing of it. */
+int qcnn_calib_gram(QcnnCtx* ctx, int H, int W, int Cin_total, int grp, int kh, int kw, int stride, int pad,
+                    const float* in_nhwc_host, int n, double* gram_inout_host, int accumulate);
+/* Refine a quantisation of one layer (the output of qcnn_quantize_layer: ctrd_init [M][K][Cs], asmt_init in file order) against
+ * gram_host [grp][P][P] (NULL = identity: J is then the k-means SSE).  Cin = channels per group, output channel ct belongs to
+ * group ct / (Ct/grp); one code book for all groups and taps (src/CaffeEva.cc:787,810).  Block (y, x, m) = the index range
+ * (y*kw + x)*Cin + m*Cs + [0, CsEff(m)); E = W - W_hat, Hm = E G.  One SWEEP = for m = 0 .. M-1:
+ *   assign   for every tap (y, x) in ascending order, all ct at once: code word c_k in place of the current one changes J by
+ *            delta_k = -2 d^T Hm[ct][b] + d^T G_bb d, d = c_k - c_cur; the smallest delta_k is taken only if it is < 0 (ties
+ *            among improvements: the lowest k); E and Hm follow before the next tap
+ *   update   code word by code word in ascending k: A_k = sum_ct sum_{b,b' in L_k(ct)} G_bb' + lambda I, v_k = sum_ct
+ *            sum_{b in L_k(ct)} Hm[ct][b] over the blocks L_k(ct) of channel ct that name k, lambda = ridge * trace(G) / P
+ *            (mean over groups); c_k = (float)(c_k + A_k^-1 v_k) (fp64 Cholesky); E and Hm follow.  A code word without
+ *            members (or with an A_k that is not positive definite) keeps its value.  kh = kw = 1: code words share no
+ *            channel, all K are solved from one state.  Dims >= CsEff stay 0.
+ * Both steps minimise J over one block of variables: J does not rise.  The search runs in fp64.  obj_trace[i] (may be NULL,
+ * [sweeps + 1]) = J after i sweeps, evaluated from scratch in fp64 from the book and assignments of that moment;
+ * changed_trace[i] (may be NULL, [sweeps]) = assignments changed in sweep i.  A sweep that changes no assignment and no code
+ * word ends the search (the remaining entries repeat the last value and 0).  Needs the shape rules of qcnn_quantize_layer,
+ * Ct % grp == 0, sweeps >= 0, ridge >= 0, finite weights / gram / book, assignments < K, a non-negative gram diagonal.
+ * Blocking; scratch per call, freed before return; a loaded model is not touched. */
+int qcnn_quantize_layer_ec(QcnnCtx* ctx, int Ct, int Cin, int grp, int kh, int kw, int M, int K, int Cs, const float* weights_host,
+                           const double* gram_host, const float* ctrd_init_host, const uint8_t* asmt_init_host, int sweeps,
+                           double ridge, float* ctrd_out_host, uint8_t* asmt_out_host, double* obj_trace, int* changed_trace);
 /* Size of the packed parameter arena (biases, permuted codebooks, permuted assignments). */
 int qcnn_model_arena_bytes(QcnnCtx* ctx, size_t* bytes);
 /* Plan buffers for up to max_batch images.  dev_arena: caller-owned device memory of

@@ -1194,6 +1194,157 @@ int qcnn_quantize_layer(QcnnCtx* c, int Ct, int Cin, int kh, int kw, int M, int 
   return 0;
 }
 
+int qcnn_calib_gram(QcnnCtx* c, int H, int W, int Cin_total, int grp, int kh, int kw, int stride, int pad, const float* in_nhwc, int n,
+                    double* gram, int accumulate) {
+  if (!c) return fail(nullptr, "qcnn_calib_gram: ctx == NULL");
+  if (H <= 0 || W <= 0 || Cin_total <= 0 || grp <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || n <= 0)
+    return fail(c, "qcnn_calib_gram: bad geometry H=%d W=%d C=%d grp=%d kh=%d kw=%d stride=%d pad=%d n=%d", H, W, Cin_total, grp, kh, kw,
+                stride, pad, n);
+  if (Cin_total % grp) return fail(c, "qcnn_calib_gram: %d channels do not divide into %d groups", Cin_total, grp);
+  if (H + 2 * pad < kh || W + 2 * pad < kw) return fail(c, "qcnn_calib_gram: a %dx%d window does not fit a %dx%d map with pad %d", kh, kw, H, W, pad);
+  if (!in_nhwc || !gram) return fail(c, "qcnn_calib_gram: in_nhwc and gram must not be NULL");
+  QkGramGeom s;
+  s.H = H; s.W = W; s.C = Cin_total; s.grp = grp; s.Cg = Cin_total / grp; s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad;
+  s.Ho = conv_out(H, kh, stride, pad);
+  s.Wo = conv_out(W, kw, stride, pad);
+  const long long Pll = (long long)kh * kw * s.Cg;
+  if (Pll > 46340) return fail(c, "qcnn_calib_gram: patch length %lld is too large", Pll);        // P * P stays below 2^31
+  s.P = (int)Pll;
+  s.rows = (long long)n * s.Ho * s.Wo;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t inElems = (size_t)n * H * W * Cin_total, gElems = (size_t)grp * s.P * s.P;
+  int splits = 1;
+  const long long per = qk_ec_gram_rows_per_split(s, (size_t)2 << 30, &splits);
+  PqScratch sc;
+  float* dIn = nullptr;
+  double *dG = nullptr, *slab = nullptr;
+  HIP_TRY(c, sc.alloc((void**)&dIn, inElems * sizeof(float)));
+  HIP_TRY(c, sc.alloc((void**)&dG, gElems * sizeof(double)));
+  HIP_TRY(c, sc.alloc((void**)&slab, gElems * sizeof(double) * splits));
+  HIP_TRY(c, hipMemcpyAsync(dIn, in_nhwc, inElems * sizeof(float), hipMemcpyHostToDevice, st));
+  if (accumulate) HIP_TRY(c, hipMemcpyAsync(dG, gram, gElems * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, qk_ec_gram(dIn, s, per, splits, slab, dG, accumulate ? 1 : 0, st));
+  HIP_TRY(c, hipMemcpyAsync(gram, dG, gElems * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return 0;
+}
+
+int qcnn_quantize_layer_ec(QcnnCtx* c, int Ct, int Cin, int grp, int kh, int kw, int M, int K, int Cs, const float* weights,
+                           const double* gram, const float* ctrd_init, const uint8_t* asmt_init, int sweeps, double ridge, float* ctrd_out,
+                           uint8_t* asmt_out, double* obj_trace, int* changed_trace) {
+  if (!c) return fail(nullptr, "qcnn_quantize_layer_ec: ctx == NULL");
+  if (Ct <= 0 || Cin <= 0 || kh <= 0 || kw <= 0) return fail(c, "qcnn_quantize_layer_ec: bad layer shape Ct=%d Cin=%d kh=%d kw=%d", Ct, Cin, kh, kw);
+  if (grp <= 0 || Ct % grp) return fail(c, "qcnn_quantize_layer_ec: Ct=%d does not divide into grp=%d groups", Ct, grp);
+  if (Cs < 1 || Cs > QCNN_PQ_MAX_CS) return fail(c, "qcnn_quantize_layer_ec: Cs=%d outside [1, %d]", Cs, QCNN_PQ_MAX_CS);
+  if (K < 2 || K > QCNN_PQ_MAX_K) return fail(c, "qcnn_quantize_layer_ec: K=%d outside [2, %d]", K, QCNN_PQ_MAX_K);
+  if (M < 1 || (long long)M * Cs < Cin) return fail(c, "qcnn_quantize_layer_ec: M*Cs = %lld does not cover Cin = %d", (long long)M * Cs, Cin);
+  if ((long long)(M - 1) * Cs >= Cin) return fail(c, "qcnn_quantize_layer_ec: sub-space %d starts beyond Cin = %d (M*Cs must be < Cin + Cs)", M - 1, Cin);
+  if (sweeps < 0) return fail(c, "qcnn_quantize_layer_ec: sweeps=%d < 0", sweeps);
+  if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(c, "qcnn_quantize_layer_ec: ridge=%g must be finite and >= 0", ridge);
+  if (!weights || !ctrd_init || !asmt_init || !ctrd_out || !asmt_out)
+    return fail(c, "qcnn_quantize_layer_ec: weights, ctrd_init, asmt_init, ctrd_out and asmt_out must not be NULL");
+  const int taps = kh * kw;
+  const long long Nll = (long long)Ct * taps, Pll = (long long)taps * Cin;
+  if (Nll * M >= (1LL << 31) || Pll > 46340) return fail(c, "qcnn_quantize_layer_ec: %lld points x %d sub-spaces x patch length %lld is too large", Nll, M, Pll);
+  QkEcShape s;
+  s.Ct = Ct; s.Cin = Cin; s.grp = grp; s.taps = taps; s.M = M; s.K = K; s.Cs = Cs; s.P = (int)Pll; s.N = (int)Nll;
+  const size_t wElems = (size_t)Nll * Cin, cbElems = (size_t)M * K * Cs, MN = (size_t)M * s.N, pp = (size_t)s.P * s.P, gElems = pp * grp;
+  for (size_t i = 0; i < wElems; ++i)
+    if (!std::isfinite(weights[i])) return fail(c, "qcnn_quantize_layer_ec: weight %zu is not finite", i);
+  std::vector<float> book(ctrd_init, ctrd_init + cbElems);
+  for (size_t i = 0; i < cbElems; ++i) {
+    if ((int)(i / ((size_t)K * Cs)) * Cs + (int)(i % Cs) >= Cin) book[i] = 0.0f;                // dims >= CsEff stay 0
+    else if (!std::isfinite(book[i])) return fail(c, "qcnn_quantize_layer_ec: code book entry %zu is not finite", i);
+  }
+  std::vector<uint8_t> a(MN);                                                                       // file order [N][M] -> device [M][N]
+  for (int n = 0; n < s.N; ++n)
+    for (int m = 0; m < M; ++m) {
+      const uint8_t v = asmt_init[(size_t)n * M + m];
+      if (v >= K) return fail(c, "qcnn_quantize_layer_ec: assignment %zu is %d, the book has %d code words", (size_t)n * M + m, (int)v, K);
+      a[(size_t)m * s.N + n] = v;
+    }
+  double lambda = ridge;                                                                           // identity: trace(G) / P = 1
+  if (gram) {
+    for (size_t i = 0; i < gElems; ++i)
+      if (!std::isfinite(gram[i])) return fail(c, "qcnn_quantize_layer_ec: gram entry %zu is not finite", i);
+    double tr = 0.0;
+    for (int g = 0; g < grp; ++g)
+      for (int p = 0; p < s.P; ++p) {
+        const double d = gram[(size_t)g * pp + (size_t)p * s.P + p];
+        if (d < 0.0) return fail(c, "qcnn_quantize_layer_ec: gram diagonal entry %d of group %d is negative (%g)", p, g, d);
+        tr += d;
+      }
+    lambda = ridge * tr / ((double)grp * s.P);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  PqScratch sc;
+  float *dW = nullptr, *ctrd = nullptr;
+  uint8_t* asmt = nullptr;
+  double *G = nullptr, *E = nullptr, *Hm = nullptr, *partial = nullptr, *dw = nullptr;
+  int *flags = nullptr, *off = nullptr, *list = nullptr;                                           // flags: chg [Ct] + moved [1]
+  const int nPart = qk_ec_objective_blocks(s);
+  HIP_TRY(c, sc.alloc((void**)&dW, wElems * sizeof(float)));
+  HIP_TRY(c, sc.alloc((void**)&ctrd, cbElems * sizeof(float)));
+  HIP_TRY(c, sc.alloc((void**)&asmt, MN));
+  HIP_TRY(c, sc.alloc((void**)&G, gElems * sizeof(double)));
+  HIP_TRY(c, sc.alloc((void**)&E, (size_t)Ct * s.P * sizeof(double)));
+  HIP_TRY(c, sc.alloc((void**)&Hm, (size_t)Ct * s.P * sizeof(double)));
+  HIP_TRY(c, sc.alloc((void**)&partial, nPart * sizeof(double)));
+  HIP_TRY(c, sc.alloc((void**)&dw, (size_t)K * Cs * sizeof(double)));
+  HIP_TRY(c, sc.alloc((void**)&flags, (Ct + 1) * sizeof(int)));
+  HIP_TRY(c, sc.alloc((void**)&off, (K + 1) * sizeof(int)));
+  HIP_TRY(c, sc.alloc((void**)&list, s.N * sizeof(int)));
+  HIP_TRY(c, hipMemcpyAsync(dW, weights, wElems * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(ctrd, book.data(), cbElems * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(asmt, a.data(), MN, hipMemcpyHostToDevice, st));
+  if (gram) {
+    HIP_TRY(c, hipMemcpyAsync(G, gram, gElems * sizeof(double), hipMemcpyHostToDevice, st));
+  } else {
+    HIP_TRY(c, qk_ec_identity(G, s.P, grp, st));
+  }
+  std::vector<double> part(nPart);
+  std::vector<int> hflags(Ct + 1);
+  // J from scratch in fp64; leaves E and Hm = E G of this moment behind, which the next sweep starts from
+  auto objective = [&](double* out) -> int {
+    HIP_TRY(c, qk_ec_evaluate(dW, ctrd, asmt, G, E, Hm, partial, s, st));
+    HIP_TRY(c, hipMemcpyAsync(part.data(), partial, nPart * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    double sum = 0.0;
+    for (double v : part) sum += v;
+    *out = sum;
+    return 0;
+  };
+  double obj = 0.0;
+  if (objective(&obj)) return 1;
+  if (obj_trace) obj_trace[0] = obj;
+  bool done = false;
+  for (int sw = 0; sw < sweeps; ++sw) {
+    int changed = 0;
+    if (!done) {
+      HIP_TRY(c, hipMemsetAsync(flags, 0, (Ct + 1) * sizeof(int), st));
+      for (int m = 0; m < M; ++m) {
+        for (int t = 0; t < taps; ++t) HIP_TRY(c, qk_ec_assign(ctrd, asmt, G, E, Hm, flags, s, m, t, st));
+        HIP_TRY(c, qk_ec_update(ctrd, asmt, off, list, G, E, Hm, dw, flags + Ct, s, m, lambda, st));
+      }
+      HIP_TRY(c, hipMemcpyAsync(hflags.data(), flags, (Ct + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      for (int i = 0; i < Ct; ++i) changed += hflags[i];
+      if (objective(&obj)) return 1;
+      done = changed == 0 && hflags[Ct] == 0;
+    }
+    if (obj_trace) obj_trace[sw + 1] = obj;
+    if (changed_trace) changed_trace[sw] = changed;
+  }
+  HIP_TRY(c, hipMemcpyAsync(ctrd_out, ctrd, cbElems * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(a.data(), asmt, MN, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < s.N; ++n) asmt_out[(size_t)n * M + m] = a[(size_t)m * s.N + n];
+  return 0;
+}
+
 int qcnn_model_arena_bytes(QcnnCtx* c, size_t* bytes) {
   if (plan_arena(c)) return 1;
   *bytes = c->arenaBytes;

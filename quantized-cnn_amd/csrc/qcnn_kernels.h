@@ -442,4 +442,28 @@ hipError_t qk_pq_update(const float* pts, float* ctrd, const uint8_t* asmt, cons
 int qk_pq_finalize_blocks(size_t total);     // doubles of the partial-sum buffer qk_pq_finalize writes
 hipError_t qk_pq_finalize(const float* dmin, size_t total, float* ctrd, int M, int K, int Cs, int Cin, double* partial, hipStream_t st);
 
+// Error-corrected quantisation (qcnn_ec.hip, behind qcnn_calib_gram / qcnn_quantize_layer_ec).  Patch index
+// p = (y * kw + x) * Cg + c; G [grp][P][P], E / Hm [Ct][P] fp64; asmt on the device [M][N], N = Ct * taps.
+#define QCNN_EC_GRAM_RUN 256     // patches k_ec_gram sums in fp32 before the sums move to fp64 (the r of its error bound, + the MFMA depth 4)
+struct QkGramGeom {
+  int H, W, C, grp, Cg, kh, kw, stride, pad, Ho, Wo, P;
+  long long rows;                // n * Ho * Wo patches
+};
+struct QkEcShape {
+  int Ct, Cin, grp, taps, M, K, Cs, P, N;
+};
+int qk_ec_gram_tiles(int P);
+long long qk_ec_gram_rows_per_split(const QkGramGeom& s, size_t maxSlabBytes, int* splits);
+// slab: splits * grp * P * P doubles; G = (accumulate ? G : 0) + the slabs in ascending order, mirrored
+hipError_t qk_ec_gram(const float* in, const QkGramGeom& s, long long rowsPerSplit, int splits, double* slab, double* G, int accumulate,
+                      hipStream_t st);
+hipError_t qk_ec_identity(double* G, int P, int grp, hipStream_t st);
+int qk_ec_objective_blocks(const QkEcShape& s);
+hipError_t qk_ec_evaluate(const float* w, const float* ctrd, const uint8_t* asmt, const double* G, double* E, double* Hm, double* partial,
+                          const QkEcShape& s, hipStream_t st);
+hipError_t qk_ec_assign(const float* ctrd, uint8_t* asmt, const double* G, double* E, double* Hm, int* chg, const QkEcShape& s, int m, int t,
+                        hipStream_t st);
+hipError_t qk_ec_update(float* ctrd, const uint8_t* asmt, int* off, int* list, const double* G, double* E, double* Hm, double* dw, int* moved,
+                        const QkEcShape& s, int m, double lambda, hipStream_t st);
+
 #endif  // QCNN_KERNELS_H_

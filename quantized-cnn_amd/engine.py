@@ -20,6 +20,9 @@ class QcnnError(RuntimeError):
 
 
 DEFAULT_MAX_ITER = 30     # Lloyd steps of quantize_layer / quantize.quantize_model unless the caller says otherwise
+DEFAULT_EC_SWEEPS = 4     # sweeps of quantize_layer_ec unless the caller says otherwise
+DEFAULT_EC_RIDGE = 1e-6   # its ridge, in units of the mean diagonal of the gram matrix
+EC_GRAM_RUN = 256         # QCNN_EC_GRAM_RUN: patches calib_gram sums in fp32 before the sums move to fp64
 
 
 class QcnnEngine:
@@ -153,6 +156,65 @@ class QcnnEngine:
                                                init.ctypes.data if init is not None else None, max_iter,
                                                ctrd.ctypes.data, asmt.ctypes.data, sse, it))
         return ctrd, asmt, dict(sse_init=float(sse[0]), sse=float(sse[1]), iters=int(it[0]), unconverged=int(it[1]))
+
+    def calib_gram(self, x_nhwc, geom, gram=None):
+        """Second moments of a layer's input windows (qcnn_calib_gram).  x_nhwc: fm[layer] of n images, [n][H][W][C] (FC: anything
+        of n rows, taken as [n][1][1][D]); geom: dict(grp, kh, kw, stride, pad) (quantize.layer_geom).  Returns float64
+        [grp][P][P], P = kh*kw*C/grp; with ``gram`` (a C-contiguous float64 array of that shape) the sums are added to it in
+        place and it is returned."""
+        x = np.ascontiguousarray(x_nhwc, np.float32)
+        if x.ndim != 4:
+            x = x.reshape(x.shape[0], 1, 1, -1)
+        n, h, w, ch = x.shape
+        grp, kh, kw = int(geom["grp"]), int(geom["kh"]), int(geom["kw"])
+        P = kh * kw * (ch // max(grp, 1))
+        acc = gram is not None
+        if acc:
+            if gram.dtype != np.float64 or gram.shape != (grp, P, P) or not gram.flags["C_CONTIGUOUS"]:
+                raise QcnnError("gram must be a C-contiguous float64 array of shape %r" % ((grp, P, P),))
+        else:
+            gram = np.empty((max(grp, 0), P, P), np.float64)
+        self._chk(self.lib.qcnn_calib_gram(self.h, h, w, ch, grp, kh, kw, int(geom["stride"]), int(geom["pad"]), x.ctypes.data, n,
+                                           gram.ctypes.data, 1 if acc else 0))
+        return gram
+
+    def quantize_layer_ec(self, weights, M, K, Cs, gram, ctrd, asmt, grp=1, sweeps=DEFAULT_EC_SWEEPS, ridge=DEFAULT_EC_RIDGE):
+        """Error-corrected refinement of a quantisation of one layer (qcnn_quantize_layer_ec): from the book ``ctrd`` [M][K][Cs]
+        and assignments ``asmt`` (file order, quantize_layer's output) minimise the response error e^T G e against ``gram``
+        [grp][P][P] (calib_gram; None = identity).  Returns (ctrd, asmt, stats dict(obj_init, obj, obj_trace [sweeps + 1],
+        changed [sweeps], sweeps = sweeps that changed something))."""
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.ndim == 4:
+            ct, cin, kh, kw = w.shape
+            ashape = (ct, kh, kw, M)
+        elif w.ndim == 2:
+            (ct, cin), kh, kw = w.shape, 1, 1
+            ashape = (ct, M)
+        else:
+            raise QcnnError("weights must be [Ct][Cin][kh][kw] or [Ct][D], got shape %r" % (w.shape,))
+        c0 = np.ascontiguousarray(ctrd, np.float32)
+        a0 = np.ascontiguousarray(asmt, np.uint8)
+        if c0.shape != (M, K, Cs):
+            raise QcnnError("ctrd must be [M][K][Cs] = %r, got %r" % ((M, K, Cs), c0.shape))
+        if a0.size != int(np.prod(ashape)):
+            raise QcnnError("asmt must have %r entries, got shape %r" % (ashape, a0.shape))
+        g = None
+        if gram is not None:
+            g = np.ascontiguousarray(gram, np.float64)
+            P = kh * kw * cin
+            if g.shape != (grp, P, P):
+                raise QcnnError("gram must be [grp][P][P] = %r, got %r" % ((grp, P, P), g.shape))
+        c1 = np.empty_like(c0)
+        a1 = np.empty(ashape, np.uint8)
+        ns = max(int(sweeps), 0)
+        obj = (C.c_double * (ns + 1))()
+        chg = (C.c_int * max(ns, 1))()
+        self._chk(self.lib.qcnn_quantize_layer_ec(self.h, ct, cin, grp, kh, kw, M, K, Cs, w.ctypes.data,
+                                                  g.ctypes.data if g is not None else None, c0.ctypes.data, a0.ctypes.data,
+                                                  int(sweeps), float(ridge), c1.ctypes.data, a1.ctypes.data, obj, chg))
+        trace, changed = np.array(obj[:], np.float64), np.array(chg[:ns], np.int64)
+        return c1, a1, dict(obj_init=float(trace[0]), obj=float(trace[-1]), obj_trace=trace, changed=changed,
+                            sweeps=int(np.count_nonzero(changed)) if ns else 0)
 
     def fm_dims(self, l):
         d = (C.c_int * 3)()

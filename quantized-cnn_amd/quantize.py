@@ -5,6 +5,8 @@ MATLAB code that was not released), run on the GPU through ``QcnnEngine.quantize
 ``quantize_model``      every conv / FC layer of a dense parameter set (synth.make_dense_params form) at the shipped layout
                         rule (synth.quant_spec); returns the params dict engine.load_model, synth.write_param_dir and
                         pyoracle.COracle.set_params take, plus per-layer statistics
+``calibrate``           second moments of every conv / FC layer's input on calibration images (the dense network's own
+                        feature maps), for the error-corrected refinement ``quantize_model(..., calib=...)`` runs after k-means
 ``quantize_param_dir``  reads ``<pfx>.biasVec`` + ``convKnl`` / ``fcntWei`` files, writes ``biasVec`` + ``ctrdLst`` +
                         ``asmtLst.cbn`` (minimum bits, CaffePara::CalcBitCntPerEle) for the reference's LoadLayerPara
 
@@ -18,8 +20,8 @@ import time
 
 import numpy as np
 
-from . import fileio, synth, topology
-from .engine import DEFAULT_MAX_ITER, QcnnEngine
+from . import capi, fileio, synth, topology
+from .engine import DEFAULT_EC_RIDGE, DEFAULT_EC_SWEEPS, DEFAULT_MAX_ITER, QcnnEngine
 from .topology import CONV, FCNT
 
 
@@ -49,11 +51,53 @@ def _layer_stats(w, ctrd, asmt, st, seconds):
     return dict(st, rel_err=rel, seconds=seconds)
 
 
-def quantize_model(eng, in_chw, layers, dense, spec=None, max_iter=DEFAULT_MAX_ITER):
+def layer_geom(layers, i):
+    """dict(grp, kh, kw, stride, pad) of conv / FC layer i as QcnnEngine.calib_gram takes it (FC: a 1x1 window on a 1x1 map)."""
+    ly = layers[i]
+    if ly["type"] == CONV:
+        return dict(grp=ly["grp"], kh=ly["knl"], kw=ly["knl"], stride=ly["stride"], pad=ly["pad"])
+    if ly["type"] == FCNT:
+        return dict(grp=1, kh=1, kw=1, stride=1, pad=0)
+    raise ValueError("layer %d is neither conv nor FC" % i)
+
+
+def layer_input(layers, i, fm_nhwc):
+    """Feature map i ([n][H][W][C], QcnnEngine.layer_output) as layer i consumes it — what run_layer and calib_gram take: a conv
+    layer reads it as it is, an FC layer the flat vector in the reference's order (channel-major: [n][C][H][W] flattened)."""
+    x = np.asarray(fm_nhwc, np.float32)
+    if layers[i]["type"] == FCNT:
+        x = x.transpose(0, 3, 1, 2).reshape(x.shape[0], 1, 1, -1)
+    return np.ascontiguousarray(x)
+
+
+def calibrate(eng, in_chw, layers, dense, imgs, chunk=32):
+    """{layer: gram [grp][P][P] float64} for every layer of ``dense``: the dense model (load_dense_model, every feature map kept)
+    forwards ``imgs`` [n][C][H][W] in chunks, and each conv / FC layer's INPUT map goes to ``eng.calib_gram``, accumulating.
+    Every layer sees the dense network's activations, so layers are corrected independently of each other.  Loads a model
+    into ``eng``: whatever it held before is replaced, and QCNN_OPT_KEEP_ALL is left at 1 (the library's default)."""
+    imgs = np.ascontiguousarray(imgs, np.float32)
+    chunk = max(1, min(int(chunk), len(imgs)))
+    eng.set_option(capi.OPT_KEEP_ALL, 1)
+    eng.load_dense_model(in_chw, layers, dense, chunk)
+    grams = {}
+    for n0 in range(0, len(imgs), chunk):
+        part = imgs[n0:n0 + chunk]
+        eng.forward_host(part, want_prob=False, want_top5=False)
+        for i in sorted(dense):
+            x = layer_input(layers, i, eng.layer_output(i, len(part)))
+            grams[i] = eng.calib_gram(x, layer_geom(layers, i), grams.get(i))
+    return grams
+
+
+def quantize_model(eng, in_chw, layers, dense, spec=None, max_iter=DEFAULT_MAX_ITER, calib=None, sweeps=DEFAULT_EC_SWEEPS,
+                   ridge=DEFAULT_EC_RIDGE):
     """Quantise every layer of ``dense`` ({layer: dict(bias, weights)}, synth.make_dense_params / the convKnl, fcntWei files)
     with ``eng.quantize_layer`` at ``spec`` (default synth.quant_spec: conv Cs = 8, K = 128; hidden FC Cs = 4, K = 32;
     classifier Cs = 1, K = 16).  Returns (params {layer: dict(bias, ctrd, asmt, bits)}, stats {layer: dict(sse_init, sse,
-    iters, unconverged, rel_err = |W - W_hat| / |W|, seconds = wall time of the call incl. copies)})."""
+    iters, unconverged, rel_err = |W - W_hat| / |W|, seconds = wall time of the call incl. copies)}).  With ``calib``
+    ({layer: gram}, the result of ``calibrate``) every layer in it is then refined by ``eng.quantize_layer_ec`` (``sweeps``,
+    ``ridge``) from the k-means result, and its stats gain obj_init, obj (response error e^T G e before / after), sweeps and
+    changed; without it the k-means result is returned as it always was."""
     spec = spec or synth.quant_spec(in_chw, layers)
     params, stats = {}, {}
     for i in sorted(dense):
@@ -63,6 +107,10 @@ def quantize_model(eng, in_chw, layers, dense, spec=None, max_iter=DEFAULT_MAX_I
         w = np.ascontiguousarray(dense[i]["weights"], np.float32)
         t0 = time.perf_counter()
         ctrd, asmt, st = eng.quantize_layer(w, s["M"], s["K"], s["Cs"], max_iter=max_iter)
+        if calib is not None and i in calib:
+            grp = layers[i]["grp"] if layers[i]["type"] == CONV else 1
+            ctrd, asmt, ec = eng.quantize_layer_ec(w, s["M"], s["K"], s["Cs"], calib[i], ctrd, asmt, grp=grp, sweeps=sweeps, ridge=ridge)
+            st = dict(st, obj_init=ec["obj_init"], obj=ec["obj"], sweeps=ec["sweeps"], changed=[int(x) for x in ec["changed"]])
         dt = time.perf_counter() - t0
         params[i] = dict(bias=np.ascontiguousarray(dense[i]["bias"], np.float32), ctrd=ctrd, asmt=asmt,
                          bits=fileio.min_bits(asmt))
@@ -91,17 +139,20 @@ def read_dense_param_dir(dir_path, prefix, layers):
     return out
 
 
-def quantize_param_dir(src_dir, src_pfx, dst_dir, dst_pfx, model, eng=None, spec=None, max_iter=DEFAULT_MAX_ITER):
+def quantize_param_dir(src_dir, src_pfx, dst_dir, dst_pfx, model, eng=None, spec=None, max_iter=DEFAULT_MAX_ITER, calib_images=None,
+                       sweeps=DEFAULT_EC_SWEEPS, ridge=DEFAULT_EC_RIDGE):
     """Quantise a dense parameter directory into a Q-CNN one.  ``model``: a name of topology.MODELS or (in_chw, layers).
-    ``eng``: anything with QcnnEngine.quantize_layer's signature (default: a QcnnEngine on device 0).  Returns the stats of
-    quantize_model."""
+    ``eng``: anything with QcnnEngine.quantize_layer's signature (default: a QcnnEngine on device 0).  ``calib_images``
+    ([n][C][H][W]): error-corrected on them (calibrate + quantize_model(calib=...)); ``eng`` then loses the model it held.
+    Returns the stats of quantize_model."""
     in_chw, layers = _model_tables(model)
     dense = read_dense_param_dir(src_dir, src_pfx, layers)
     own = eng is None
     if own:
         eng = QcnnEngine(0)
     try:
-        params, stats = quantize_model(eng, in_chw, layers, dense, spec=spec, max_iter=max_iter)
+        calib = calibrate(eng, in_chw, layers, dense, calib_images) if calib_images is not None else None
+        params, stats = quantize_model(eng, in_chw, layers, dense, spec=spec, max_iter=max_iter, calib=calib, sweeps=sweeps, ridge=ridge)
     finally:
         if own:
             eng.close()
