@@ -966,25 +966,10 @@ hipError_t qk_conv_dec(const DecParams& p, hipStream_t st) {
   return launch_dec<2, 2, false, 3, 4>(p, st);
 }
 
-bool qk_fc_dec_shape(int D, int M, int Cs, int Ct, int* S) {
-  if (Cs != 1 || M != D || D % 64 || Ct < 1) return false;
-  if ((size_t)D * PANEL * sizeof(float) >= (1ull << 32)) return false;
-  *S = (Ct + 63) / 64 * 64;
-  return (size_t)D * *S * sizeof(float) < (1ull << 32);
-}
-
 hipError_t qk_decode_fc_weights(const uint8_t* rows, const float* ctrd, float* out, const QkSlots& sl, int D, int K, int Ct,
                                 int S, hipStream_t st) {
   hipLaunchKernelGGL(k_decode_fc_weights, dim3(2048), dim3(256), 0, st, rows, ctrd, out, sl, D, K, Ct, S);
   return hipGetLastError();
-}
-
-int qk_fc_dec_slices(int D, int Ct, int panels, int live) {
-  // k slices over workgroups: until the launch has about a workgroup per CU, every wave keeping >= 4 steps
-  const int wgs = ((Ct + 63) / 64) * panels * ((live + 63) / 64);
-  int z = 1;
-  while (wgs * z < 192 && D % (64 * 2 * z) == 0 && D / (64 * 2 * z) >= 4 && 2 * z <= 32) z *= 2;   // <= 32 slabs of scratch per sub-batch
-  return z;
 }
 
 hipError_t qk_fc_dec(const FcDecParams& p, int slices, int live, hipStream_t st) {

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <map>
 #include <string>
@@ -25,6 +26,12 @@ namespace {
 
 std::string g_createError = "";
 
+// The tables a layer's arena may hold beside bias, code book and the plain assignment rows, in the order plan_arena lays them
+// out (kTables, below, says when a layer has which, and how it is built)
+enum TableKind { T_PROG16, T_SLIDE16, T_SYM16, T_FC8, T_CBN, T_HALF8, T_HALF8_SLIDE, T_SYM8, T_SYM8_SLIDE, T_COUNT };
+enum BookKind { BOOK_NONE = -1, BOOK_FC8, BOOK_CONV8, BOOK_COUNT };    // qk_ctrdf_index / qk_ctrd8_index order
+struct Span { size_t off = 0, bytes = 0; };
+
 struct LayerShape {
   int M = 0, K = 0, Cs = 0;                                    // as the kernels see the layer (K <= 128)
   int P = 1, Mfile = 0, Kfile = 0;                             // a parameter set with 128 < K <= 256 code words per sub-space: every sub-space is P =
@@ -33,17 +40,9 @@ struct LayerShape {
   size_t offDense = 0, denseFloats = 0;
   size_t offBias = 0, offCtrd = 0, offAsmt = 0, offDmap = 0;   // byte offsets into the arena
   size_t asmtBytes = 0;
-  size_t offProg = 0, progBytes = 0;                           // conv with K = 128: offsets in consumption order (QkProgram)
-  size_t offProgS = 0, progSBytes = 0;                         // ... and in the order of the sliding variant, where it applies
-  size_t offProgY = 0, progYBytes = 0;                         // ... and of the symmetric kernel's (8 channels per wave, 2x2 tile) layout
-  size_t offProg8 = 0, prog8Bytes = 0;                         // ... and of the eight-wave symmetric kernel's layout (Qk8Config)
-  size_t offProg8S = 0, prog8SBytes = 0;                       // ... and of its sliding form (qk_conv_sym8_slide_config)
-  size_t offProgH8 = 0, progH8Bytes = 0;                       // ... and of the half-panel eight-wave kernel (QkH8Config, qcnn_half8.hip)
-  size_t offProgH8S = 0, progH8SBytes = 0;                     // ... and of its sliding form (qk_conv_half8_slide_config)
-  size_t offCtrd8 = 0;                                         // ... with the code book in that kernel's operand order (qk_ctrd8_index)
-  size_t offProgF8 = 0, progF8Bytes = 0, offCtrdF = 0;         // FC with 32 code words of 4 dims: program + code book of the eight-wave kernel (k_fc_sym8)
-  size_t offCbn = 0, cbnBytes = 0; int cbnBits = 0;            // FC: the assignments bit-packed as the .cbn payload holds them (file order
-                                                               // [Ct][M], include/FileIO.h:128-166), read in place by the few-image kernel
+  Span tab[T_COUNT];                                           // the per-family tables (kTables, in arena order); bytes = 0: the layer has none
+  size_t offBook[BOOK_COUNT] = {0}; bool hasBook[BOOK_COUNT] = {false};   // the code book in the eight-wave kernels' operand orders
+  int cbnBits = 0;                                             // bits per assignment of the T_CBN span
   size_t offDecN = 0; int decNV = 0;                          // first layer: the same code words in k_conv_dec_nchw's order; decNV: its padded k (0: not eligible)
   size_t offDecB = 0; int decBK = 0;                          // ... split into three bf16 pieces for k_conv_dec_nchw_split; decBK: its padded k (0: not eligible)
   size_t offDec = 0; int decKp = 0, decS = 0;                  // decoded code words (qcnn_decoded.hip): conv layer with one sub-space of
@@ -53,13 +52,11 @@ struct LayerShape {
   // QCNN_OPT_LUT_MODE = 2 (fp16 table storage): the eight-wave kernels' program tables with offsets into the fp16 table layout.
   // Own allocations, built from the arena's assignment bytes when the mode first runs the layer (every rank of a group builds
   // its own from the broadcast arena); dropped when the layer's parameters are uploaded again
-  uint16_t* prog8H = nullptr;
-  uint16_t* progF8H = nullptr;
-  uint16_t* prog8A = nullptr;        // QCNN_OPT_LUT_MODE = 3 (fp16 sums too): the program of the twice-as-large tiles (qk_conv_sym8_config16)
+  uint16_t* progF16[2][T_COUNT] = {{nullptr}};                  // [0]: fp16 tables, [1]: QCNN_OPT_LUT_MODE = 3's twice-as-large tiles (T_SYM8 only)
   // conv: launch plans (qcnn_planner.h) by launch geometry and options (panels, sub-batches, split / slide / sym, LUT mode, input
   // in place): sub-batches of unequal panel counts (3 panels over 2 streams) each keep theirs instead of evicting one another —
   // a plan is dozens of 256-CU list schedules on the host
-  std::map<long long, QkConvPlan> plans;
+  std::map<std::array<int, 10>, QkConvPlan> plans;
   int segN = 0, segBeg[9] = {0};                               // segments of the last launch when it slid (qcnn_get_layer_segments)
   int lastFrom = -1, lastZ = 1;                                // how the last launch was actually cut
 };
@@ -70,7 +67,6 @@ constexpr int kProfRing = 32;    // forwards whose per-layer events are kept
 constexpr int kMaxStreams = 4;   // sub-batches (streams) of one forward
 constexpr int kSmallBatchMax = QCNN_SMALL_BATCH_MAX;  // batches up to this size run the few-image kernels (QCNN_OPT_SMALL_BATCH): beyond, a
                                    // 128-image panel is cheaper (measured: 1 / 2 / 3 / 4 images 0.58 / 0.85 / 1.15 / 1.47 ms, a panel 1.50 ms)
-constexpr int kMaxFcSplit = 32;  // workgroups along the sub-space axis of an FC layer (partial sums reduced in fixed order)
 constexpr size_t kConvPartialFloats = (size_t)64 << 20;   // 256 MB of partial sums for split conv tiles (all sub-batches), allocated when a plan first splits
 constexpr size_t kSlack = 64 * 1024;   // bytes of slack behind every device buffer: the MFMA operand loads are
                                         // unconditional and may read a few rows past the last dim / sub-space
@@ -169,6 +165,132 @@ int pool_out(int in, int knl, int stride, int pad) {          // ceil mode, src/
 
 size_t fm_elems(const QcnnCtx* c, int l) { return (size_t)c->dims[l].h * c->dims[l].w * c->dims[l].c; }
 
+template <class T> T* arena_at(const QcnnCtx* c, size_t off) { return reinterpret_cast<T*>(c->arena + off); }
+// a layer's table of one kind; nullptr: it has none
+const uint16_t* table(const QcnnCtx* c, const LayerShape& s, int kind) {
+  return s.tab[kind].bytes ? arena_at<const uint16_t>(c, s.tab[kind].off) : nullptr;
+}
+
+// The reference's .cbn packing of `bits`-bit values (include/FileIO.h:299-341): 4096-byte blocks of floor(32768 / bits) values, MSB
+// first, no value across a block; bits <= 8, so a value touches at most two bytes
+size_t cbn_size(size_t n, int bits) { const size_t per = 4096 * 8 / (size_t)bits; return (n + per - 1) / per * 4096; }
+unsigned cbn_get(const uint8_t* blocks, size_t e, int bits) {
+  const size_t per = 4096 * 8 / (size_t)bits, bit0 = (e % per) * bits;
+  const uint8_t* b = blocks + (e / per) * 4096 + (bit0 >> 3);
+  const unsigned w = ((unsigned)b[0] << 8) | (unsigned)b[(bit0 & 7) + bits > 8 ? 1 : 0];
+  return (w >> (16 - (bit0 & 7) - bits)) & ((1u << bits) - 1u);
+}
+void cbn_put(uint8_t* blocks, size_t e, int bits, unsigned v) {      // into zeroed blocks
+  const size_t per = 4096 * 8 / (size_t)bits, bit0 = (e % per) * bits;
+  uint8_t* b = blocks + (e / per) * 4096 + (bit0 >> 3);
+  const unsigned w = v << (16 - (bit0 & 7) - bits);
+  b[0] |= (uint8_t)(w >> 8);
+  if (w & 0xffu) b[1] |= (uint8_t)(w & 0xffu);
+}
+int cbn_bits(int K) {               // the reference's CalcBitCntPerEle for K code words (src/CaffePara.cc:360-380)
+  int bits = 1;
+  while ((1 << bits) < K) ++bits;
+  return bits;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// kTables: the one place that knows, per TableKind, when a layer has the table and how big it is, and how it is built from the
+// arena's assignment rows.  (Layers of pseudo sub-spaces — more than 128 code words, P > 1 — always run the exact-builder
+// kernels, which read the plain rows: they have none of these.)
+// ------------------------------------------------------------------------------------------------------------------
+struct TableGeom {
+  bool conv;                        // else FC: Cin = its D input dims, grp = knl = stride = 1
+  int Cin, Ct, grp, knl, stride;
+  int M, Cs, K, P;
+  QkSlots sl;                       // of the plain assignment rows (QkSlots, qcnn_kernels.h)
+};
+TableGeom table_geom(const QcnnCtx* c, int l) {
+  const QcnnLayerDesc& d = c->layers[l];
+  const LayerShape& s = c->shapes[l];
+  const int Ct = c->dims[l + 1].c;
+  if (d.type == QCNN_CONV) return {true, c->dims[l].c, Ct, d.grpCnt, d.knlSiz, d.stride, s.M, s.Cs, s.K, s.P, qk_conv_slots(Ct / d.grpCnt, d.grpCnt)};
+  return {false, (int)fm_elems(c, l), Ct, 1, 1, 1, s.M, s.Cs, s.K, s.P, qk_fc_slots(Ct)};
+}
+
+// 16-wave conv kernels (K = 128): offsets in consumption order (QkProgram) for the tile kernel, its sliding variant where it
+// applies, and the symmetric kernel's (8 channels per wave, 2x2 tile) layout.  pg.rfH = 0: the layer has no such table
+struct Layout16 { QkSlots dst; QkProgram pg; int slide; };
+Layout16 layout16(const TableGeom& g, int kind) {
+  Layout16 y = {g.sl, QkProgram{}, 0};
+  if (!g.conv || g.P != 1) return y;
+  if (kind == T_SYM16) {
+    if (!qk_conv_sym_shape(g.Cin, g.grp, g.Ct, g.M, g.Cs, g.K)) return y;
+    y.dst = qk_make_slots(g.sl.C, g.sl.groups, 8);
+    y.pg = qk_conv_program(y.dst, g.knl, g.stride);
+  } else if (g.K == 128 && kind == T_PROG16) {
+    y.pg = qk_conv_program(g.sl, g.knl, g.stride);
+  } else if (g.K == 128) {
+    const QkSlide sc = qk_slide_config(g.sl.C, g.sl.groups, g.knl, g.stride);
+    if (sc.ns == 0) return y;
+    y.dst = sc.sl; y.slide = 1;
+    y.pg = qk_conv_program_slide(sc.sl, sc.ns, sc.nc, g.knl, g.stride);
+  }
+  return y;
+}
+template <int KIND> size_t bytes16(const TableGeom& g, int) {
+  const QkProgram pg = layout16(g, KIND).pg;
+  return (size_t)pg.rfH * pg.rfW * g.M * pg.rowU16 * sizeof(uint16_t);
+}
+template <int KIND> hipError_t build16(const TableGeom& g, const uint8_t* rows, uint16_t* out, hipStream_t st, int) {
+  const Layout16 y = layout16(g, KIND);
+  return qk_build_program(rows, out, g.sl, y.dst, y.pg, g.knl, g.stride, g.M, st, y.slide);
+}
+
+// eight-wave symmetric kernel (Qk8Config) and its sliding form; v = 2: the twice-as-large tiles of QCNN_OPT_LUT_MODE = 3
+Qk8Config cfg_sym8(const TableGeom& g, int v) {
+  return v == 2 ? qk_conv_sym8_config16(g.Cin, g.grp, g.Ct, g.M, g.Cs, g.K) : qk_conv_sym8_config(g.Cin, g.grp, g.Ct, g.M, g.Cs, g.K);
+}
+Qk8Config cfg_sym8_slide(const TableGeom& g, int) { return qk_conv_sym8_slide_config(g.Cin, g.grp, g.Ct, g.M, g.Cs, g.K, g.knl, g.stride); }
+template <Qk8Config (*CFG)(const TableGeom&, int)> size_t bytes8(const TableGeom& g, int v) {
+  return g.conv && g.P == 1 ? qk_conv_sym8_program_bytes(CFG(g, v), g.grp, g.knl, g.stride, g.M) : 0;
+}
+template <Qk8Config (*CFG)(const TableGeom&, int)> hipError_t build8(const TableGeom& g, const uint8_t* rows, uint16_t* out, hipStream_t st, int v) {
+  return qk_build_program8(rows, out, g.sl, CFG(g, v), g.Ct / g.grp, g.grp, g.knl, g.stride, g.M, st, v ? 1 : 0);
+}
+
+// half-panel eight-wave kernel (QkH8Config, qcnn_half8.hip) and its sliding form
+QkH8Config cfg_half8(const TableGeom& g) { return qk_conv_half8_config(g.Cin, g.grp, g.Ct, g.M, g.Cs, g.K); }
+QkH8Config cfg_half8_slide(const TableGeom& g) { return qk_conv_half8_slide_config(g.Cin, g.grp, g.Ct, g.M, g.Cs, g.K, g.knl, g.stride); }
+template <QkH8Config (*CFG)(const TableGeom&)> size_t bytes_h8(const TableGeom& g, int) {
+  return g.conv && g.P == 1 ? qk_conv_half8_program_bytes(CFG(g), g.grp, g.knl, g.stride, g.M) : 0;
+}
+template <QkH8Config (*CFG)(const TableGeom&)> hipError_t build_h8(const TableGeom& g, const uint8_t* rows, uint16_t* out, hipStream_t st, int) {
+  return qk_build_program_h8(rows, out, g.sl, CFG(g), g.Ct / g.grp, g.grp, g.knl, g.stride, g.M, st);
+}
+
+// FC with 32 code words of 4 dims: the eight-wave kernel's program (k_fc_sym8), uint16 offsets in its channel order
+size_t bytes_fc8(const TableGeom& g, int) {
+  return !g.conv && g.P == 1 && qk_fc_sym8_shape(g.Cin, g.Ct, g.M, g.Cs, g.K) ? qk_fc_sym8_program_bytes(g.Ct, g.M) : 0;
+}
+hipError_t build_fc8(const TableGeom& g, const uint8_t* rows, uint16_t* out, hipStream_t st, int v) {
+  return qk_build_program_fc8(rows, out, g.sl, g.Ct, g.M, st, v ? 1 : 0);
+}
+// FC: the assignments bit-packed as the .cbn payload holds them (file order [Ct][M], include/FileIO.h:128-166), read in place
+// by the few-image kernel; written by the upload itself (upload_packed_assignments)
+size_t bytes_cbn(const TableGeom& g, int) { return !g.conv && g.P == 1 ? cbn_size((size_t)g.Ct * g.M, cbn_bits(g.K)) : 0; }
+
+struct TableDesc {
+  size_t (*bytes)(const TableGeom& g, int v);      // 0: the layer has none.  v = 0: the arena's table; 1 / 2: its fp16 forms (ensure_f16_program)
+  hipError_t (*build)(const TableGeom& g, const uint8_t* rows, uint16_t* out, hipStream_t st, int v);
+  BookKind book;                                   // the code book in the kernel's operand order goes with it: one copy, laid out
+};                                                 // behind the last of the (consecutive) kinds that name it
+const TableDesc kTables[T_COUNT] = {
+    /* T_PROG16      */ {bytes16<T_PROG16>, build16<T_PROG16>, BOOK_NONE},
+    /* T_SLIDE16     */ {bytes16<T_SLIDE16>, build16<T_SLIDE16>, BOOK_NONE},
+    /* T_SYM16       */ {bytes16<T_SYM16>, build16<T_SYM16>, BOOK_NONE},
+    /* T_FC8         */ {bytes_fc8, build_fc8, BOOK_FC8},
+    /* T_CBN         */ {bytes_cbn, nullptr, BOOK_NONE},
+    /* T_HALF8       */ {bytes_h8<cfg_half8>, build_h8<cfg_half8>, BOOK_CONV8},
+    /* T_HALF8_SLIDE */ {bytes_h8<cfg_half8_slide>, build_h8<cfg_half8_slide>, BOOK_CONV8},
+    /* T_SYM8        */ {bytes8<cfg_sym8>, build8<cfg_sym8>, BOOK_CONV8},
+    /* T_SYM8_SLIDE  */ {bytes8<cfg_sym8_slide>, build8<cfg_sym8_slide>, BOOK_CONV8},
+};
+
 int plan_arena(QcnnCtx* c) {
   size_t off = 0;
   for (int l = 0; l < c->L; ++l) {
@@ -176,77 +298,36 @@ int plan_arena(QcnnCtx* c) {
     if (d.type != QCNN_CONV && d.type != QCNN_FCNT) continue;
     LayerShape& s = c->shapes[l];
     const int Ct = c->dims[l + 1].c;
+    s.hasDmap = (d.type == QCNN_FCNT && l == c->firstFc && c->dims[l].h * c->dims[l].w > 1);
     if (s.dense) {                     // precise path: bias + weights [grp][taps][Cin/grp][Ct/grp]
       s.offBias = off; off = align_up(off + sizeof(float) * Ct, 256);
       const size_t taps = (d.type == QCNN_CONV) ? (size_t)d.knlSiz * d.knlSiz : 1;
       const size_t cin = (d.type == QCNN_CONV) ? (size_t)c->dims[l].c / d.grpCnt : fm_elems(c, l);
       s.denseFloats = taps * cin * Ct;
       s.offDense = off; off = align_up(off + sizeof(float) * s.denseFloats, 256);
-      s.hasDmap = (d.type == QCNN_FCNT && l == c->firstFc && c->dims[l].h * c->dims[l].w > 1);
       if (s.hasDmap) { s.offDmap = off; off = align_up(off + sizeof(int) * fm_elems(c, l), 256); }
       continue;
     }
     if (s.K <= 0) return fail(c, "layer %d: neither a quantisation shape (qcnn_model_set_layer_shape) nor dense weights (qcnn_model_set_layer_dense) declared", l);
+    const size_t bookBytes = sizeof(float) * (size_t)s.M * s.Cs * s.K;
     s.offBias = off; off = align_up(off + sizeof(float) * Ct, 256);
-    s.offCtrd = off; off = align_up(off + sizeof(float) * (size_t)s.M * s.Cs * s.K, 256);
+    s.offCtrd = off; off = align_up(off + bookBytes, 256);
     // assignment table: one-byte row slots in the order the gather waves consume them (QkSlots, qcnn_kernels.h)
-    const QkSlots sl = (d.type == QCNN_CONV) ? qk_conv_slots(Ct / d.grpCnt, d.grpCnt) : qk_fc_slots(Ct);
+    const TableGeom g = table_geom(c, l);
     const size_t taps = (d.type == QCNN_CONV) ? (size_t)d.knlSiz * d.knlSiz : 1;
-    s.asmtBytes = taps * s.M * sl.rowStride;
+    s.asmtBytes = taps * s.M * g.sl.rowStride;
     s.offAsmt = off; off = align_up(off + s.asmtBytes + QCNN_ROWS_PAD, 256);
-    s.progBytes = 0;
-    // (layers of pseudo sub-spaces — more than 128 code words, s.P > 1 — always run the exact-builder kernel, which reads the plain
-    // table: none of the program tables / operand-order code books below is built for them)
-    if (d.type == QCNN_CONV && s.K == 128 && s.P == 1) {     // the MFMA panel kernel reads its offsets through the program table
-      const QkProgram pg = qk_conv_program(sl, d.knlSiz, d.stride);
-      s.progBytes = (size_t)pg.rfH * pg.rfW * s.M * pg.rowU16 * sizeof(uint16_t);
-      s.offProg = off; off = align_up(off + s.progBytes + QCNN_ROWS_PAD, 256);
-      s.progSBytes = 0;
-      const QkSlide sc = qk_slide_config(Ct / d.grpCnt, d.grpCnt, d.knlSiz, d.stride);
-      if (sc.ns > 0) {
-        const QkProgram ps = qk_conv_program_slide(sc.sl, sc.ns, sc.nc, d.knlSiz, d.stride);
-        s.progSBytes = (size_t)ps.rfH * ps.rfW * s.M * ps.rowU16 * sizeof(uint16_t);
-        s.offProgS = off; off = align_up(off + s.progSBytes + QCNN_ROWS_PAD, 256);
-      }
+    for (bool& has : s.hasBook) has = false;
+    for (int k = 0; k < T_COUNT; ++k) {
+      s.tab[k] = Span{0, kTables[k].bytes(g, 0)};
+      if (s.tab[k].bytes) { s.tab[k].off = off; off = align_up(off + s.tab[k].bytes + QCNN_ROWS_PAD, 256); }
+      const int b = kTables[k].book;
+      if (b == BOOK_NONE) continue;
+      s.hasBook[b] = s.hasBook[b] || s.tab[k].bytes;
+      if (s.hasBook[b] && (k + 1 == T_COUNT || kTables[k + 1].book != b)) { s.offBook[b] = off; off = align_up(off + bookBytes, 256); }
     }
-    s.progYBytes = 0;
-    if (d.type == QCNN_CONV && s.P == 1 && qk_conv_sym_shape(c->dims[l].c, d.grpCnt, Ct, s.M, s.Cs, s.K)) {
-      const QkProgram py = qk_conv_program(qk_make_slots(Ct / d.grpCnt, d.grpCnt, 8), d.knlSiz, d.stride);
-      s.progYBytes = (size_t)py.rfH * py.rfW * s.M * py.rowU16 * sizeof(uint16_t);
-      s.offProgY = off; off = align_up(off + s.progYBytes + QCNN_ROWS_PAD, 256);
-    }
-    s.progF8Bytes = 0;
-    if (d.type == QCNN_FCNT && s.P == 1 && qk_fc_sym8_shape((int)fm_elems(c, l), Ct, s.M, s.Cs, s.K)) {
-      s.progF8Bytes = qk_fc_sym8_program_bytes(Ct, s.M);
-      s.offProgF8 = off; off = align_up(off + s.progF8Bytes + QCNN_ROWS_PAD, 256);
-      s.offCtrdF = off; off = align_up(off + sizeof(float) * (size_t)s.M * s.Cs * s.K, 256);
-    }
-    s.cbnBytes = 0;
-    if (d.type == QCNN_FCNT && s.P == 1) {           // bits = the reference's CalcBitCntPerEle for K code words (src/CaffePara.cc:360-380)
-      s.cbnBits = 1;
-      while ((1 << s.cbnBits) < s.K) ++s.cbnBits;
-      const size_t per = 4096 * 8 / (size_t)s.cbnBits;
-      s.cbnBytes = ((size_t)Ct * s.M + per - 1) / per * 4096;
-      s.offCbn = off; off = align_up(off + s.cbnBytes + 256, 256);
-    }
-    s.prog8Bytes = 0; s.prog8SBytes = 0; s.progH8Bytes = 0; s.progH8SBytes = 0;
-    if (d.type == QCNN_CONV && s.P == 1) {
-      const Qk8Config c8 = qk_conv_sym8_config(c->dims[l].c, d.grpCnt, Ct, s.M, s.Cs, s.K);
-      s.prog8Bytes = qk_conv_sym8_program_bytes(c8, d.grpCnt, d.knlSiz, d.stride, s.M);
-      const Qk8Config c8s = qk_conv_sym8_slide_config(c->dims[l].c, d.grpCnt, Ct, s.M, s.Cs, s.K, d.knlSiz, d.stride);
-      s.prog8SBytes = qk_conv_sym8_program_bytes(c8s, d.grpCnt, d.knlSiz, d.stride, s.M);
-      const QkH8Config ch8 = qk_conv_half8_config(c->dims[l].c, d.grpCnt, Ct, s.M, s.Cs, s.K);
-      s.progH8Bytes = qk_conv_half8_program_bytes(ch8, d.grpCnt, d.knlSiz, d.stride, s.M);
-      if (s.progH8Bytes) { s.offProgH8 = off; off = align_up(off + s.progH8Bytes + QCNN_ROWS_PAD, 256); }
-      const QkH8Config ch8s = qk_conv_half8_slide_config(c->dims[l].c, d.grpCnt, Ct, s.M, s.Cs, s.K, d.knlSiz, d.stride);
-      s.progH8SBytes = qk_conv_half8_program_bytes(ch8s, d.grpCnt, d.knlSiz, d.stride, s.M);
-      if (s.progH8SBytes) { s.offProgH8S = off; off = align_up(off + s.progH8SBytes + QCNN_ROWS_PAD, 256); }
-      if (s.prog8Bytes) { s.offProg8 = off; off = align_up(off + s.prog8Bytes + QCNN_ROWS_PAD, 256); }
-      if (s.prog8SBytes) { s.offProg8S = off; off = align_up(off + s.prog8SBytes + QCNN_ROWS_PAD, 256); }
-      if (s.prog8Bytes || s.prog8SBytes || s.progH8Bytes) { s.offCtrd8 = off; off = align_up(off + sizeof(float) * (size_t)s.M * s.Cs * s.K, 256); }
-    }
+    s.cbnBits = s.tab[T_CBN].bytes ? cbn_bits(s.K) : 0;
     s.decKp = 0;
-    s.hasDmap = (d.type == QCNN_FCNT && l == c->firstFc && c->dims[l].h * c->dims[l].w > 1);
     if (d.type == QCNN_CONV && qk_conv_dec_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, &s.decKp, &s.decS)) {
       s.offDec = off; off = align_up(off + sizeof(float) * (size_t)d.knlSiz * s.decKp * s.decS, 256);
       s.decNV = 0;
@@ -270,10 +351,11 @@ int plan_arena(QcnnCtx* c) {
 }
 
 void drop_f16_programs(LayerShape& s) {
-  if (s.prog8H) (void)hipFree(s.prog8H);
-  if (s.progF8H) (void)hipFree(s.progF8H);
-  if (s.prog8A) (void)hipFree(s.prog8A);
-  s.prog8H = nullptr; s.progF8H = nullptr; s.prog8A = nullptr;
+  for (auto& form : s.progF16)
+    for (uint16_t*& t : form) {
+      if (t) (void)hipFree(t);
+      t = nullptr;
+    }
 }
 
 void free_model(QcnnCtx* c) {
@@ -351,391 +433,305 @@ int ensure_pipeline(QcnnCtx* c) {
   return 0;
 }
 
-// One layer on `panels` panels: src/dst in panel layout.  flatFcInput: the FC input rows are already
-// in consumption order (qcnn_run_layer), so the NCHW-flatten map is not applied.
-// p0: first panel of the sub-batch (offsets into the scratch buffers), st: the stream it runs on
-// live: images every panel of this launch holds (128, or the batch size of a single-panel forward); small: the
-// few-image kernels (qcnn_small.hip) run the conv/FC layers
-// sub / nsub: index and number of the sub-batches (streams) of this forward: each has its own share of the scratch
 // Does conv layer l run through its decoded code words (qcnn_decoded.hip)?  The f32 MFMA mode only: the exact
 // builder keeps the reference's summation order and the fp16 study is about the tables themselves.
 bool decoded_layer(const QcnnCtx* c, int l) {
   const LayerShape& s = c->shapes[l];
   return c->decode && s.decKp > 0 && !s.dense && c->lutMode == 1 && c->layers[l].type == QCNN_CONV;
 }
-bool decoded_fc(const QcnnCtx* c, int l) {
-  const LayerShape& s = c->shapes[l];
-  return c->decode && s.decKp < 0 && !s.dense && c->lutMode == 1 && c->layers[l].type == QCNN_FCNT;
+
+// fp16 table storage (QCNN_OPT_LUT_MODE = 2 / 3): the layer's table of `kind` (T_SYM8, T_FC8) in the fp16 layout's offsets, built by
+// the kind's own builder at first use; the build runs on `st`, in front of the launch that reads it.  nullptr: failed (c->err).
+// The pointer is published in the LayerShape only once its build has been enqueued without error: on any failure behind the
+// hipMalloc the allocation is released, so that a later forward builds again instead of launching with an unbuilt table
+const uint16_t* ensure_f16_program(QcnnCtx* c, int l, int kind, hipStream_t st) {
+  LayerShape& s = c->shapes[l];
+  const int v = (kind == T_SYM8 && c->lutMode == 3) ? 2 : 1;     // fp16 sums too: the program of the twice-as-large tiles
+  if (s.progF16[v - 1][kind]) return s.progF16[v - 1][kind];
+  const TableGeom g = table_geom(c, l);
+  const size_t bytes = kTables[kind].bytes(g, v) + QCNN_ROWS_PAD + (v == 2 ? 4096 : 0);
+  uint16_t* t = nullptr;
+  hipError_t e = hipMalloc(&t, bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(t, 0, bytes, st);
+  if (e == hipSuccess) e = kTables[kind].build(g, arena_at<const uint8_t>(c, s.offAsmt), t, st, v);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);       // once per layer: the other sub-batch streams of this forward read the table too
+  if (e != hipSuccess) {
+    (void)hipFree(t);
+    fail(c, "layer %d: fp16 program table -> %s", l, hipGetErrorString(e));
+    return nullptr;
+  }
+  return s.progF16[v - 1][kind] = t;
 }
 
-// fp16 table storage: the layer's program table in the fp16 layout's offsets (first use; the build runs on `st`, in front of the
-// launch that reads it)
-// a table pointer is published in the LayerShape only once its build has been enqueued without error: on any failure behind the
-// hipMalloc the allocation is released, so that a later forward builds again instead of launching with an unbuilt table
-#define F16_TRY(ptr, expr)                                                              \
-  do {                                                                                  \
-    const hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess) {                                                             \
-      (void)hipFree(ptr);                                                               \
-      return fail(c, "%s -> %s", #expr, hipGetErrorString(e_));                         \
-    }                                                                                   \
-  } while (0)
-int ensure_f16_program(QcnnCtx* c, int l, hipStream_t st) {
-  const QcnnLayerDesc& d = c->layers[l];
-  LayerShape& s = c->shapes[l];
-  const int Ct = c->dims[l + 1].c;
-  bool built = false;
-  if (d.type == QCNN_CONV && s.prog8Bytes && c->lutMode == 3 && !s.prog8A) {
-    built = true;
-    const Qk8Config cf = qk_conv_sym8_config16(c->dims[l].c, d.grpCnt, Ct, s.M, s.Cs, s.K);
-    const size_t bytes = qk_conv_sym8_program_bytes(cf, d.grpCnt, d.knlSiz, d.stride, s.M);
-    uint16_t* t = nullptr;
-    HIP_TRY(c, hipMalloc(&t, bytes + QCNN_ROWS_PAD + 4096));
-    F16_TRY(t, hipMemsetAsync(t, 0, bytes + QCNN_ROWS_PAD + 4096, st));
-    F16_TRY(t, qk_build_program8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), t, qk_conv_slots(Ct / d.grpCnt, d.grpCnt),
-                                 cf, Ct / d.grpCnt, d.grpCnt, d.knlSiz, d.stride, s.M, st, 1));
-    s.prog8A = t;
-  }
-  if (d.type == QCNN_CONV && s.prog8Bytes && c->lutMode == 2 && !s.prog8H) {
-    built = true;
-    uint16_t* t = nullptr;
-    HIP_TRY(c, hipMalloc(&t, s.prog8Bytes + QCNN_ROWS_PAD));
-    F16_TRY(t, hipMemsetAsync(t, 0, s.prog8Bytes + QCNN_ROWS_PAD, st));
-    F16_TRY(t, qk_build_program8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), t, qk_conv_slots(Ct / d.grpCnt, d.grpCnt),
-                                 qk_conv_sym8_config(c->dims[l].c, d.grpCnt, Ct, s.M, s.Cs, s.K), Ct / d.grpCnt, d.grpCnt, d.knlSiz,
-                                 d.stride, s.M, st, 1));
-    s.prog8H = t;
-  }
-  if (d.type == QCNN_FCNT && s.progF8Bytes && !s.progF8H) {
-    uint16_t* t = nullptr;
-    HIP_TRY(c, hipMalloc(&t, s.progF8Bytes + QCNN_ROWS_PAD));
-    F16_TRY(t, hipMemsetAsync(t, 0, s.progF8Bytes + QCNN_ROWS_PAD, st));
-    F16_TRY(t, qk_build_program_fc8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), t, qk_fc_slots(Ct), Ct, s.M, st, 1));
-    s.progF8H = t;
-  } else if (!built) {
-    return 0;
-  }
-  HIP_TRY(c, hipStreamSynchronize(st));       // once per layer: the other sub-batch streams of this forward read the table too
+// One layer on `panels` panels: the per-launch facts (run_layers and qcnn_run_layer fill them)
+struct Launch {
+  const float* src; float* dst;    // in panel layout
+  int panels, p0;                  // p0: first panel of the sub-batch (offsets into the scratch buffers)
+  hipStream_t st;                  // the stream the sub-batch runs on
+  const float* inNchw = nullptr;   // the network input, read in place by the first layer (src unused)
+  int nImages = 0;                 // ... its images
+  int live = QCNN_PANEL;           // images every panel of this launch holds (128, or the batch size of a single-panel forward)
+  bool small = false;              // the few-image kernels (qcnn_small.hip) run the conv/FC layers
+  int sub = 0, nsub = 1;           // index and number of the sub-batches (streams) of this forward: each has its own share of the scratch
+  int panelsAll = 0;               // panels of ALL sub-batches of this forward (they run concurrently on their own streams and share the
+                                   // 256 CUs); 0 = this launch is alone
+  bool fuseRelu = false;
+  bool flatFcInput = false;        // the FC input rows are already in consumption order (qcnn_run_layer): no NCHW-flatten map
+};
+
+int launched(QcnnCtx* c, int l, hipError_t e) {
+  if (e != hipSuccess) return fail(c, "layer %d (type %d) launch failed: %s", l, c->layers[l].type, hipGetErrorString(e));
   return 0;
 }
 
-int launch_layer(QcnnCtx* c, int l, const float* src, float* dst, int panels, bool fuseRelu, bool flatFcInput,
-                 int p0, hipStream_t st, const float* inNchw = nullptr, int nImages = 0, int live = QCNN_PANEL,
-                 bool small = false, int sub = 0, int nsub = 1, int panelsAll = 0) {
-  // panelsAll: panels of ALL sub-batches of this forward (they run concurrently on their own streams and share the 256 CUs); 0 = this
-  // launch is alone
+// Partial-sum scratch.  Split conv tiles: kConvPartialFloats shared by the nsub sub-batches, allocated by the first split launch
+// of this context; when the device has no memory left for it (large maps at a large batch) the tiles run whole, which needs
+// none — never a failed forward.  FC layers: every sub-batch has its own slab of QK_MAX_FC_SPLIT x (its panels) x (widest layer)
+float* conv_partial(QcnnCtx* c, const Launch& L) {
+  if (!c->convPartial && !c->noConvPartial && hipMalloc(&c->convPartial, kConvPartialFloats * sizeof(float)) != hipSuccess) {
+    (void)hipGetLastError();
+    c->convPartial = nullptr; c->noConvPartial = true;
+  }
+  return c->convPartial ? c->convPartial + kConvPartialFloats / (size_t)L.nsub * L.sub : nullptr;
+}
+size_t fc_partial_offset(const QcnnCtx* c, const Launch& L) { return (size_t)QK_MAX_FC_SPLIT * L.p0 * c->fcMaxCt * QCNN_PANEL; }
+size_t fc_partial_left(const QcnnCtx* c, const Launch& L) {
+  const size_t poff = fc_partial_offset(c, L);
+  return c->fcPartialElems > poff ? c->fcPartialElems - poff : 0;
+}
+
+// what ConvParams and DecParams share: source (a panel map, or the network input read in place), destination, map geometry
+template <class P> void conv_geom(P& q, const QcnnCtx* c, int l, const Launch& L) {
+  const QcnnLayerDesc& d = c->layers[l];
+  const FmDims& a = c->dims[l];
+  const FmDims& b = c->dims[l + 1];
+  q.src = L.src; q.dst = L.dst;
+  q.srcNchw = 0; q.nImages = 0; q.panel0 = 0;
+  if (L.inNchw) { q.src = L.inNchw; q.srcNchw = 1; q.nImages = L.nImages; q.panel0 = L.p0; }
+  q.bias = arena_at<const float>(c, c->shapes[l].offBias);
+  q.H = a.h; q.W = a.w; q.Cin = a.c; q.Ho = b.h; q.Wo = b.w; q.Ct = b.c;
+  q.knl = d.knlSiz; q.stride = d.stride; q.pad = d.padSiz;
+  q.relu = L.fuseRelu ? 1 : 0; q.panels = L.panels;
+}
+
+// precise path (qcnn_dense.hip): a conv layer, or an FC layer as a 1x1 conv on a 1x1 map
+int launch_dense(QcnnCtx* c, int l, const Launch& L, const float* src, const FmDims& a, const FmDims& b, int knl, int stride, int pad, int grp) {
+  const LayerShape& s = c->shapes[l];
+  DenseParams q;
+  q.src = src; q.dst = L.dst;
+  q.bias = arena_at<const float>(c, s.offBias);
+  q.wt = arena_at<const float>(c, s.offDense);
+  q.H = a.h; q.W = a.w; q.Cin = a.c; q.Ho = b.h; q.Wo = b.w; q.Ct = b.c;
+  q.knl = knl; q.stride = stride; q.pad = pad; q.grp = grp;
+  q.relu = L.fuseRelu ? 1 : 0; q.panels = L.panels;
+  return launched(c, l, qk_dense(q, L.st));
+}
+
+int launch_conv(QcnnCtx* c, int l, const Launch& L) {
   const QcnnLayerDesc& d = c->layers[l];
   const FmDims& a = c->dims[l];
   const FmDims& b = c->dims[l + 1];
   LayerShape& s = c->shapes[l];
-  hipError_t e = hipSuccess;
-  switch (d.type) {
-    case QCNN_CONV: {
-      if (!s.loaded) return fail(c, "layer %d: parameters not uploaded", l);
-      if (s.dense) {                       // precise path (CalcFeatMap_ConvPrec, src/CaffeEva.cc:681-758)
-        DenseParams q;
-        q.src = src; q.dst = dst;
-        q.bias = reinterpret_cast<const float*>(c->arena + s.offBias);
-        q.wt = reinterpret_cast<const float*>(c->arena + s.offDense);
-        q.H = a.h; q.W = a.w; q.Cin = a.c; q.Ho = b.h; q.Wo = b.w; q.Ct = b.c;
-        q.knl = d.knlSiz; q.stride = d.stride; q.pad = d.padSiz; q.grp = d.grpCnt;
-        q.relu = fuseRelu ? 1 : 0; q.panels = panels;
-        e = qk_dense(q, st);
-        break;
-      }
-      // one sub-space of <= 4 dims: decoded code words on the matrix pipe.  Batches of one to three images too when the layer
-      // reads the NCHW input in place: a 16-image tile with one live image still beats the few-image table kernel, whose
-      // workgroups rebuild the pixel tables five times (AlexNet conv1 at one image: 0.126 -> 0.0xx ms)
-      if (decoded_layer(c, l) && (small ? (inNchw && s.decNV && c->directDec) : (!inNchw || s.decNV))) {
-        DecParams q;
-        q.src = src; q.dst = dst;
-        q.srcNchw = 0; q.nImages = 0; q.panel0 = 0;
-        if (inNchw) { q.src = inNchw; q.srcNchw = 1; q.nImages = nImages; q.panel0 = p0; }   // network input read in place
-        q.bias = reinterpret_cast<const float*>(c->arena + s.offBias);
-        q.wdec = reinterpret_cast<const float*>(c->arena + (inNchw ? s.offDecN : s.offDec));
-        q.H = a.h; q.W = a.w; q.Cin = a.c; q.Ho = b.h; q.Wo = b.w; q.Ct = b.c;
-        q.knl = d.knlSiz; q.stride = d.stride; q.pad = d.padSiz;
-        q.Kr = d.knlSiz * a.c; q.Kp = s.decKp; q.S = s.decS;
-        if (inNchw) { q.Kr = d.knlSiz * d.knlSiz * a.c; q.Kp = s.decNV; q.S = b.c; }
-        q.relu = fuseRelu ? 1 : 0; q.panels = panels; q.live = live;
-        s.lastFrom = -3; s.lastZ = inNchw ? 2 : 1;        // reported by qcnn_get_layer_split as (-3, 1), NCHW in place: (-3, 2)
-        const bool splitBf16 = inNchw && c->decSplit && s.decBK > 0;   // fp32-accurate split-bf16 products (QCNN_OPT_DEC_BF16SPLIT)
-        if (splitBf16) { q.Kp = s.decBK; q.wdec = reinterpret_cast<const float*>(c->arena + s.offDecB); }
-        e = splitBf16 ? qk_conv_dec_nchw_split(q, st) : inNchw ? qk_conv_dec_nchw(q, st) : qk_conv_dec(q, st);
-        if (e != hipErrorInvalidValue) break;             // (a map beyond the kernel's 32-bit byte offsets: the table kernel below)
-      }
-      ConvParams p;
-      p.src = src; p.dst = dst;
-      p.srcNchw = 0; p.nImages = 0; p.panel0 = 0;
-      if (inNchw) { p.src = inNchw; p.srcNchw = 1; p.nImages = nImages; p.panel0 = p0; }   // network input read in place
-      p.bias = reinterpret_cast<const float*>(c->arena + s.offBias);
-      p.ctrd = reinterpret_cast<const float*>(c->arena + s.offCtrd);
-      p.ctrd8 = (s.prog8Bytes || s.prog8SBytes || s.progH8Bytes) ? reinterpret_cast<const float*>(c->arena + s.offCtrd8) : nullptr;
-      p.rows = reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt);
-      p.prog = s.progBytes ? reinterpret_cast<const uint16_t*>(c->arena + s.offProg) : nullptr;
-      p.H = a.h; p.W = a.w; p.Cin = a.c; p.Ho = b.h; p.Wo = b.w; p.Ct = b.c;
-      p.knl = d.knlSiz; p.stride = d.stride; p.pad = d.padSiz; p.grp = d.grpCnt;
-      p.M = s.M; p.Cs = s.Cs; p.K = s.K; p.pd = s.P; p.relu = fuseRelu ? 1 : 0; p.panels = panels;
-      // few-image kernel unless the layer's shape is outside what it covers (a tap window x K that does not fit its LDS
-      // table): the panel kernel handles every shape set_layer_shape accepts
-      p.splitFrom = 0; p.splitZ = 1; p.partial = nullptr;
-      p.nSeg = 0; p.progS = s.progSBytes ? reinterpret_cast<const uint16_t*>(c->arena + s.offProgS) : nullptr;
-      s.lastFrom = -1; s.lastZ = 1;
-      if (s.P > 1) {                       // more than 128 code words per sub-space: pseudo sub-spaces, exact-builder kernel in every mode
-        e = qk_conv_aprx(p, 0, st);
-        break;
-      }
-      e = small ? qk_conv_small(p, live, st) : hipErrorInvalidValue;
-      // fp16 table storage (QCNN_OPT_LUT_MODE = 2): the eight-wave tile kernel in its fp16 form wherever the layer's shape has one
-      // (K = 128, complete 4- / 8-dim sub-spaces, > 64 channels per group); QCNN_OPT_SYM8 = 0 keeps every layer in the 16-wave
-      // kernels, which round the same entries and keep them in f32 slots (same sums, same bits: the tests compare the two)
-      // QCNN_OPT_LUT_MODE = 3 keeps the running sums as packed fp16 as well (twice the tile per wave); layers without an fp16
-      // form round their entries and keep fp32 sums in both modes
-      if (e == hipErrorInvalidValue && c->lutMode >= 2 && c->sym8 && s.prog8Bytes && !inNchw) {
-        if (ensure_f16_program(c, l, st)) return 1;
-        p.progS = c->lutMode == 3 ? s.prog8A : s.prog8H;
-        s.lastFrom = c->lutMode == 3 ? -8 : -7; s.lastZ = 1;   // reported by qcnn_get_layer_split as (-7 / -8 fp16 sums, 1)
-        e = qk_conv_sym8(p, st, c->lutMode == 3 ? 2 : 1);
-        break;
-      }
-      if (e == hipErrorInvalidValue) {
-        // Which kernel family runs this launch, and how it is cut: the planner (qcnn_planner.h) prices every eligible family for
-        // this launch geometry — cached per layer —, its decision rules pick one.  MFMA builders only: the exact builder keeps
-        // the tile kernel and the reference's summation order.
-        if (c->lutMode >= 1 && (c->split || c->slide || c->sym || c->sym8 || c->half8)) {
-          const size_t share = kConvPartialFloats / (size_t)nsub;
-          QkPlanOptions o = {};
-          o.split = c->split; o.slide = c->slide; o.sym = c->sym; o.sym8 = c->sym8; o.half8 = c->half8;
-          o.lutMode = c->lutMode; o.inNchw = inNchw ? 1 : 0; o.scratchFloats = share;
-          o.concurrent = (nsub > 1 && panelsAll > panels) ? 1 : 0;
-          o.hasSlide16 = s.progSBytes != 0; o.hasSym16 = s.progYBytes != 0; o.hasSym8 = s.prog8Bytes != 0;
-          o.hasSym8Slide = s.prog8SBytes != 0; o.hasHalf8 = s.progH8Bytes != 0; o.hasHalf8Slide = s.progH8SBytes != 0;
-          const long long key = (((((((((long long)(nsub > 1 ? panelsAll : 0) * 4096 + panels) * 8 + nsub) * 2 + (c->split ? 1 : 0)) * 4 + c->slide) * 4 + c->sym) * 4 +
-                                  c->lutMode) * 2 + (inNchw ? 1 : 0)) * 8 + c->sym8) * 4 + c->half8;
-          auto it = s.plans.find(key);
-          if (it == s.plans.end()) {
-            // Sub-batches on several streams run CONCURRENTLY: the tail of one sub-batch's launch fills with the other's workgroups
-            // (that is what the streams are for), so the family is chosen for the panels of the whole forward — planned per
-            // sub-batch, a 1000-image forward on two streams took the kernels of a 500-image one (conv3 / conv4 back on the 16-wave
-            // tile kernel) and lost what the overlap gained: 103.8 k images/s against 107 k with the one-stream plan's kernels.
-            ConvParams pp = p;
-            if (o.concurrent) pp.panels = panelsAll;
-            it = s.plans.emplace(key, qk_plan_conv(pp, o)).first;
-          }
-          const QkConvChoice ch = qk_choose_conv(it->second, o);
-          // partial sums of split tiles: scratch allocated by the first split launch of this context; when the device has no
-          // memory left for it (large maps at a large batch) the tiles run whole, which needs none — never a failed forward
-          auto partial = [&]() -> float* {
-            if (!c->convPartial && !c->noConvPartial && hipMalloc(&c->convPartial, kConvPartialFloats * sizeof(float)) != hipSuccess) {
-              (void)hipGetLastError();
-              c->convPartial = nullptr; c->noConvPartial = true;
-            }
-            return c->convPartial ? c->convPartial + share * sub : nullptr;
-          };
-          auto segments = [&]() {
-            p.nSeg = ch.nSeg; s.segN = ch.nSeg;
-            for (int i = 0; i <= ch.nSeg; ++i) { p.segBeg[i] = ch.segBeg[i]; s.segBeg[i] = ch.segBeg[i]; }
-          };
-          s.lastFrom = ch.family; s.lastZ = 1;         // what qcnn_get_layer_split reports: (family code, slices / segments)
-          bool launched = true;
-          switch (ch.family) {
-            case QK_FAM_HALF8_SLIDE:
-              p.progS = reinterpret_cast<const uint16_t*>(c->arena + s.offProgH8S);
-              segments(); s.lastZ = ch.nSeg;
-              e = qk_conv_half8_slide(p, st);
-              break;
-            case QK_FAM_HALF8:
-              p.progS = reinterpret_cast<const uint16_t*>(c->arena + s.offProgH8);
-              e = qk_conv_half8(p, st);
-              break;
-            case QK_FAM_SYM8_SLIDE:
-              p.progS = reinterpret_cast<const uint16_t*>(c->arena + s.offProg8S);
-              segments(); s.lastZ = ch.nSeg;
-              e = qk_conv_sym8_slide(p, st);
-              break;
-            case QK_FAM_SYM8:
-              p.progS = reinterpret_cast<const uint16_t*>(c->arena + s.offProg8);
-              if (ch.Z > 1) {
-                if (float* ps = partial()) { p.splitFrom = 0; p.splitZ = ch.Z; p.partial = ps; s.lastZ = ch.Z; }
-              }
-              e = qk_conv_sym8(p, st);
-              break;
-            case QK_FAM_SYM16:
-              p.progS = reinterpret_cast<const uint16_t*>(c->arena + s.offProgY);
-              e = qk_conv_sym(p, st);
-              break;
-            case QK_FAM_SLIDE16:
-              segments(); s.lastZ = ch.nSeg;
-              launched = false;                          // k_conv_aprx<.., SLIDE> below (p.progS = the sliding program)
-              break;
-            default:                                     // tile kernel, whole or with a split tail
-              s.lastFrom = -1;
-              if (ch.Z > 1) {
-                if (float* ps = partial()) {
-                  p.splitFrom = ch.splitFrom; p.splitZ = ch.Z; p.partial = ps;
-                  s.lastFrom = ch.splitFrom; s.lastZ = ch.Z;
-                }
-              }
-              launched = false;
-              break;
-          }
-          if (launched) break;
-        }
-        e = qk_conv_aprx(p, c->lutMode, st);
-      }
-      break;
-    }
-    case QCNN_FCNT: {
-      if (!s.loaded) return fail(c, "layer %d: parameters not uploaded", l);
-      if (s.dense) {                       // precise path (CalcFeatMap_FCntPrec, src/CaffeEva.cc:932-966): a 1x1 conv on a 1x1 map
-        DenseParams q;
-        q.src = src; q.dst = dst;
-        if (s.hasDmap && !flatFcInput) {
-          float* flat = c->fcFlat + (size_t)p0 * fm_elems(c, l) * QCNN_PANEL;
-          e = qk_permute_rows(src, flat, reinterpret_cast<const int*>(c->arena + s.offDmap), a.h * a.w * a.c, panels, live, st);
-          if (e != hipSuccess) break;
-          q.src = flat;
-        }
-        q.bias = reinterpret_cast<const float*>(c->arena + s.offBias);
-        q.wt = reinterpret_cast<const float*>(c->arena + s.offDense);
-        q.H = 1; q.W = 1; q.Cin = a.h * a.w * a.c; q.Ho = 1; q.Wo = 1; q.Ct = b.c;
-        q.knl = 1; q.stride = 1; q.pad = 0; q.grp = 1;
-        q.relu = fuseRelu ? 1 : 0; q.panels = panels;
-        e = qk_dense(q, st);
-        break;
-      }
-      if (decoded_fc(c, l)) {              // one-dim sub-spaces: decoded code words on the matrix pipe (qcnn_decoded.hip)
-        FcDecParams q;
-        q.src = src; q.dst = dst; q.partial = nullptr;
-        q.bias = reinterpret_cast<const float*>(c->arena + s.offBias);
-        q.wdec = reinterpret_cast<const float*>(c->arena + s.offDec);
-        q.D = a.h * a.w * a.c; q.Ct = b.c; q.S = s.decS;
-        q.relu = fuseRelu ? 1 : 0; q.panels = panels; q.halves = 2;
-        // k slices over workgroups change the summation order with the panel count of the launch: QCNN_OPT_SPLIT only (off =
-        // batch-size-invariant bits, as for the split conv tiles and the per-launch FC split below)
-        int z = c->split ? std::min(qk_fc_dec_slices(q.D, q.Ct, panels, live), kMaxFcSplit) : 1;
-        const size_t need = (size_t)z * panels * q.Ct * QCNN_PANEL;
-        const size_t poff = (size_t)kMaxFcSplit * p0 * c->fcMaxCt * QCNN_PANEL;    // every sub-batch has its own slab
-        if (z > 1 && poff + need <= c->fcPartialElems) q.partial = c->fcPartial + poff; else z = 1;
-        s.lastFrom = -3; s.lastZ = z;        // reported by qcnn_get_layer_split as (-3, k slices over workgroups)
-        e = qk_fc_dec(q, z, live, st);
-        if (e == hipSuccess && z > 1)
-          e = qk_sum_partials(q.partial, dst, z, (size_t)panels * q.Ct * QCNN_PANEL, q.relu, st);
-        break;
-      }
-      s.lastFrom = -1; s.lastZ = 1;
-      FcParams p;
-      p.src = src; p.dst = dst;
-      p.bias = reinterpret_cast<const float*>(c->arena + s.offBias);
-      p.ctrd = reinterpret_cast<const float*>(c->arena + s.offCtrd);
-      p.rows = reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt);
-      p.cbn = (s.cbnBytes && c->packedFc) ? reinterpret_cast<const uint8_t*>(c->arena + s.offCbn) : nullptr;
-      p.cbnBits = s.cbnBits;
-      if (s.hasDmap && !flatFcInput) {   // NHWC -> consumption order (NCHW flatten) into the scratch map
-        float* flat = c->fcFlat + (size_t)p0 * fm_elems(c, l) * QCNN_PANEL;
-        e = qk_permute_rows(src, flat, reinterpret_cast<const int*>(c->arena + s.offDmap), a.h * a.w * a.c,
-                            panels, live, st);
-        if (e != hipSuccess) break;
-        p.src = flat;
-      }
-      p.D = a.h * a.w * a.c; p.Ct = b.c; p.M = s.M; p.Cs = s.Cs; p.K = s.K; p.pd = s.P;
-      p.relu = fuseRelu ? 1 : 0; p.panels = panels;
-      // Split the sub-space axis over workgroups when the (channel chunk x panel) grid cannot fill the
-      // chip; the exact builder keeps one pass so that the summation order stays the reference's.
-      p.msplit = 1; p.partial = nullptr;
-      if (s.P > 1) {                       // pseudo sub-spaces: one pass of the exact-builder kernel
-        e = qk_fc_aprx(p, 0, st);
-        break;
-      }
-      if (small && s.K % 4 == 0 && (size_t)live * s.M * s.K <= c->fcPartialElems) {
-        p.partial = c->fcPartial;          // few images: the tables are materialised in the partial-sum scratch
-        e = qk_fc_small(p, live, st);      // (K not a multiple of 4: the panel kernel below)
-        if (e != hipErrorInvalidValue) break;
-        p.partial = nullptr;
-      }
-      // k_fc_sym8: 768 channels per workgroup.  A launch of one or two panels stays with the 12-wave kernel's 384 (measured,
-      // AlexNet fc6 / fc7 per 125 images: 0.092 / 0.053 against 0.108 / 0.070 ms; 250: 0.148 / 0.076 against 0.150 / 0.082; 500:
-      // 0.304 / 0.135 against 0.259 / 0.129) — under QCNN_OPT_SPLIT only, whose results may depend on the batch size
-      const bool fc8h = s.progF8Bytes && c->sym8 && c->lutMode >= 2 && !small;      // fp16 table storage (3: fp16 sums too): always the eight-wave form
-      const bool fc8 = fc8h || (s.progF8Bytes && c->sym8 && c->lutMode == 1 && !small && (c->sym8 >= 2 || !c->split || panels >= 3));
-      if (c->lutMode >= 1) {
-        const int G = qcnn_stage_group(s.K);
-        const int stages = (s.M + G - 1) / G;
-        // batch-independent choice (a given image must produce the same bits in any batch): the split count
-        // that fills 256 CUs best at the design point of 8 panels (1000 images) while every workgroup keeps
-        // >= 24 stages (>= 12 when that leaves a single panel — one GPU's share of a sharded batch — on fewer than 64
-        // CUs); ties go to fewer splits.  (A grid of chunks x splits x panels workgroups runs in
-        // ceil(grid / 256) rounds: 528 workgroups cost as much as 768.)
-        const int cpb = qk_fc_channels_per_block(p.Ct);
-        const int chunks = fc8 ? qk_fc_sym8_chunks(p.Ct) : (p.Ct + cpb - 1) / cpb;
-        auto pick = [&](int minStages) {
-          int best = 1;
-          double bestFill = 0.0;
-          for (int cand = 1; cand <= kMaxFcSplit; ++cand) {
-            if (cand > 1 && stages / cand < minStages) break;
-            const int grid = chunks * cand * 8;
-            const double fill = (double)grid / (256.0 * ((grid + 255) / 256));
-            if (fill > bestFill + 1e-9) { bestFill = fill; best = cand; }
-          }
-          return best;
-        };
-        int ms = pick(24);
-        if (chunks * ms < 64) ms = pick(12);     // few channel chunks (a 1000-way classifier): a single panel would sit on < 64 CUs
-        if (c->split && chunks * ms * panels < 2 * 256) {
-          // QCNN_OPT_SPLIT: a launch of a few panels (one GPU's share of a sharded batch) picks the split for ITS panel
-          // count (the bits of an image then depend on the batch size, to rounding): >= 8 stages per workgroup, fewest
-          // rounds of 256 workgroups x stages each, ties to fewer splits
-          int best = ms;
-          double bestT = 1e30;
-          for (int cand = 1; cand <= kMaxFcSplit; ++cand) {
-            if (cand > 1 && stages / cand < 8) break;
-            const int grid = chunks * cand * panels;
-            const double t = (double)((grid + 255) / 256) * ((double)((stages + cand - 1) / cand) + 10.0) + 0.5 * cand;
-            if (t < bestT - 1e-9) { bestT = t; best = cand; }
-          }
-          ms = best;
-        }
-        const size_t need = (size_t)ms * panels * p.Ct * QCNN_PANEL;
-        const size_t poff = (size_t)kMaxFcSplit * p0 * c->fcMaxCt * QCNN_PANEL;    // every sub-batch has its own slab
-        if (ms > 1 && poff + need <= c->fcPartialElems) { p.msplit = ms; p.partial = c->fcPartial + poff; }
-      }
-      if (fc8) {
-        // every workgroup along the sub-space axis needs a stage: the count the launcher will accept for this split
-        const int stagesF = s.M / 4, per = (stagesF + p.msplit - 1) / p.msplit;
-        p.msplit = (stagesF + per - 1) / per;
-        if (p.msplit == 1) p.partial = nullptr;
-        s.lastFrom = fc8h ? (c->lutMode == 3 ? -8 : -7) : -5; s.lastZ = p.msplit;   // reported by qcnn_get_layer_split as (-5 / -7 fp16 tables / -8 fp16 sums, splits of the sub-space axis)
-        if (fc8h && ensure_f16_program(c, l, st)) return 1;
-        e = qk_fc_sym8(p, fc8h ? s.progF8H : reinterpret_cast<const uint16_t*>(c->arena + s.offProgF8),
-                       reinterpret_cast<const float*>(c->arena + s.offCtrdF), st, fc8h ? (c->lutMode == 3 ? 2 : 1) : 0);
-      } else {
-        e = qk_fc_aprx(p, c->lutMode, st);
-      }
-      if (e == hipSuccess && p.msplit > 1)
-        e = qk_sum_partials(p.partial, dst, p.msplit, (size_t)panels * p.Ct * QCNN_PANEL, p.relu, st);
-      break;
-    }
-    case QCNN_POOL:
-      e = qk_pool(src, dst, panels, a.h, a.w, a.c, b.h, b.w, d.knlSiz, d.stride, d.padSiz, live, st);
-      break;
-    case QCNN_RELU:
-      e = qk_relu(src, dst, (size_t)panels * fm_elems(c, l) * QCNN_PANEL, st);
-      break;
-    case QCNN_LORN:
-      e = qk_lrn(src, dst, panels, a.h * a.w, a.c, d.lrnSiz, d.lrnAlp, d.lrnBet, d.lrnIni, live, st);
-      break;
-    case QCNN_DRPT:   // test-time dropout is a copy (src/CaffeEva.cc:1091-1096); only reached by qcnn_run_layer
-      e = hipMemcpyAsync(dst, src, (size_t)panels * fm_elems(c, l) * QCNN_PANEL * sizeof(float),
-                         hipMemcpyDeviceToDevice, st);
-      break;
-    case QCNN_SMAX:
-      e = qk_softmax(src, dst, panels, a.h * a.w * a.c, live, st);
-      break;
-    default:
-      return fail(c, "layer %d: invalid layer type %d", l, d.type);
+  const float* inNchw = L.inNchw;
+  hipStream_t st = L.st;
+  if (!s.loaded) return fail(c, "layer %d: parameters not uploaded", l);
+  // precise path (CalcFeatMap_ConvPrec, src/CaffeEva.cc:681-758)
+  if (s.dense) return launch_dense(c, l, L, L.src, a, b, d.knlSiz, d.stride, d.padSiz, d.grpCnt);
+  // one sub-space of <= 4 dims: decoded code words on the matrix pipe.  Batches of one to three images too when the layer
+  // reads the NCHW input in place: a 16-image tile with one live image still beats the few-image table kernel, whose
+  // workgroups rebuild the pixel tables five times (AlexNet conv1 at one image: 0.126 -> 0.0xx ms)
+  if (decoded_layer(c, l) && (L.small ? (inNchw && s.decNV && c->directDec) : (!inNchw || s.decNV))) {
+    DecParams q;
+    conv_geom(q, c, l, L);
+    q.wdec = arena_at<const float>(c, inNchw ? s.offDecN : s.offDec);
+    q.Kr = d.knlSiz * a.c; q.Kp = s.decKp; q.S = s.decS;
+    if (inNchw) { q.Kr = d.knlSiz * d.knlSiz * a.c; q.Kp = s.decNV; q.S = b.c; }
+    q.live = L.live;
+    s.lastFrom = -3; s.lastZ = inNchw ? 2 : 1;        // reported by qcnn_get_layer_split as (-3, 1), NCHW in place: (-3, 2)
+    const bool splitBf16 = inNchw && c->decSplit && s.decBK > 0;   // fp32-accurate split-bf16 products (QCNN_OPT_DEC_BF16SPLIT)
+    if (splitBf16) { q.Kp = s.decBK; q.wdec = arena_at<const float>(c, s.offDecB); }
+    const hipError_t e = splitBf16 ? qk_conv_dec_nchw_split(q, st) : inNchw ? qk_conv_dec_nchw(q, st) : qk_conv_dec(q, st);
+    if (e != hipErrorInvalidValue) return launched(c, l, e);   // (a map beyond the kernel's 32-bit byte offsets: the table kernel below)
   }
-  if (e != hipSuccess) return fail(c, "layer %d (type %d) launch failed: %s", l, d.type, hipGetErrorString(e));
-  return 0;
+  ConvParams p;
+  conv_geom(p, c, l, L);
+  p.ctrd = arena_at<const float>(c, s.offCtrd);
+  p.ctrd8 = s.hasBook[BOOK_CONV8] ? arena_at<const float>(c, s.offBook[BOOK_CONV8]) : nullptr;
+  p.rows = arena_at<const uint8_t>(c, s.offAsmt);
+  p.prog = table(c, s, T_PROG16);
+  p.grp = d.grpCnt;
+  p.M = s.M; p.Cs = s.Cs; p.K = s.K; p.pd = s.P;
+  p.splitFrom = 0; p.splitZ = 1; p.partial = nullptr;
+  p.nSeg = 0; p.progS = table(c, s, T_SLIDE16);
+  s.lastFrom = -1; s.lastZ = 1;
+  // more than 128 code words per sub-space: pseudo sub-spaces, exact-builder kernel in every mode
+  if (s.P > 1) return launched(c, l, qk_conv_aprx(p, 0, st));
+  // few-image kernel unless the layer's shape is outside what it covers (a tap window x K that does not fit its LDS
+  // table): the panel kernel handles every shape set_layer_shape accepts
+  if (L.small) {
+    const hipError_t e = qk_conv_small(p, L.live, st);
+    if (e != hipErrorInvalidValue) return launched(c, l, e);
+  }
+  // fp16 table storage (QCNN_OPT_LUT_MODE = 2): the eight-wave tile kernel in its fp16 form wherever the layer's shape has one
+  // (K = 128, complete 4- / 8-dim sub-spaces, > 64 channels per group); QCNN_OPT_SYM8 = 0 keeps every layer in the 16-wave
+  // kernels, which round the same entries and keep them in f32 slots (same sums, same bits: the tests compare the two)
+  // QCNN_OPT_LUT_MODE = 3 keeps the running sums as packed fp16 as well (twice the tile per wave); layers without an fp16
+  // form round their entries and keep fp32 sums in both modes
+  if (c->lutMode >= 2 && c->sym8 && s.tab[T_SYM8].bytes && !inNchw) {
+    if (!(p.progS = ensure_f16_program(c, l, T_SYM8, st))) return 1;
+    s.lastFrom = c->lutMode == 3 ? -8 : -7; s.lastZ = 1;   // reported by qcnn_get_layer_split as (-7 / -8 fp16 sums, 1)
+    return launched(c, l, qk_conv_sym8(p, st, c->lutMode == 3 ? 2 : 1));
+  }
+  // Which kernel family runs this launch, and how it is cut: the planner (qcnn_planner.h) prices every eligible family for
+  // this launch geometry — cached per layer —, its decision rules pick one.  MFMA builders only: the exact builder keeps
+  // the tile kernel and the reference's summation order.
+  if (c->lutMode >= 1 && (c->split || c->slide || c->sym || c->sym8 || c->half8)) {
+    QkPlanOptions o = {};
+    o.split = c->split; o.slide = c->slide; o.sym = c->sym; o.sym8 = c->sym8; o.half8 = c->half8;
+    o.lutMode = c->lutMode; o.inNchw = inNchw ? 1 : 0; o.scratchFloats = kConvPartialFloats / (size_t)L.nsub;
+    o.concurrent = (L.nsub > 1 && L.panelsAll > L.panels) ? 1 : 0;
+    o.hasSlide16 = s.tab[T_SLIDE16].bytes != 0; o.hasSym16 = s.tab[T_SYM16].bytes != 0; o.hasSym8 = s.tab[T_SYM8].bytes != 0;
+    o.hasSym8Slide = s.tab[T_SYM8_SLIDE].bytes != 0; o.hasHalf8 = s.tab[T_HALF8].bytes != 0; o.hasHalf8Slide = s.tab[T_HALF8_SLIDE].bytes != 0;
+    const std::array<int, 10> key = {L.nsub > 1 ? L.panelsAll : 0, L.panels, L.nsub, c->split ? 1 : 0, c->slide, c->sym, c->lutMode, inNchw ? 1 : 0, c->sym8, c->half8};
+    auto it = s.plans.find(key);
+    if (it == s.plans.end()) {
+      // Sub-batches on several streams run CONCURRENTLY: the tail of one sub-batch's launch fills with the other's workgroups
+      // (that is what the streams are for), so the family is chosen for the panels of the whole forward — planned per
+      // sub-batch, a 1000-image forward on two streams took the kernels of a 500-image one (conv3 / conv4 back on the 16-wave
+      // tile kernel) and lost what the overlap gained: 103.8 k images/s against 107 k with the one-stream plan's kernels.
+      ConvParams pp = p;
+      if (o.concurrent) pp.panels = L.panelsAll;
+      it = s.plans.emplace(key, qk_plan_conv(pp, o)).first;
+    }
+    const QkConvChoice ch = qk_choose_conv(it->second, o);
+    auto segments = [&]() {
+      p.nSeg = ch.nSeg; s.segN = ch.nSeg; s.lastZ = ch.nSeg;
+      for (int i = 0; i <= ch.nSeg; ++i) { p.segBeg[i] = ch.segBeg[i]; s.segBeg[i] = ch.segBeg[i]; }
+    };
+    s.lastFrom = ch.family; s.lastZ = 1;         // what qcnn_get_layer_split reports: (family code, slices / segments)
+    switch (ch.family) {
+      case QK_FAM_HALF8_SLIDE:
+        p.progS = table(c, s, T_HALF8_SLIDE);
+        segments();
+        return launched(c, l, qk_conv_half8_slide(p, st));
+      case QK_FAM_HALF8:
+        p.progS = table(c, s, T_HALF8);
+        return launched(c, l, qk_conv_half8(p, st));
+      case QK_FAM_SYM8_SLIDE:
+        p.progS = table(c, s, T_SYM8_SLIDE);
+        segments();
+        return launched(c, l, qk_conv_sym8_slide(p, st));
+      case QK_FAM_SYM8:
+        p.progS = table(c, s, T_SYM8);
+        if (ch.Z > 1) {
+          if (float* ps = conv_partial(c, L)) { p.splitFrom = 0; p.splitZ = ch.Z; p.partial = ps; s.lastZ = ch.Z; }
+        }
+        return launched(c, l, qk_conv_sym8(p, st));
+      case QK_FAM_SYM16:
+        p.progS = table(c, s, T_SYM16);
+        return launched(c, l, qk_conv_sym(p, st));
+      case QK_FAM_SLIDE16:
+        segments();                                // k_conv_aprx<.., SLIDE> below (p.progS = the sliding program)
+        break;
+      default:                                     // tile kernel, whole or with a split tail
+        s.lastFrom = -1;
+        if (ch.Z > 1) {
+          if (float* ps = conv_partial(c, L)) {
+            p.splitFrom = ch.splitFrom; p.splitZ = ch.Z; p.partial = ps;
+            s.lastFrom = ch.splitFrom; s.lastZ = ch.Z;
+          }
+        }
+        break;
+    }
+  }
+  return launched(c, l, qk_conv_aprx(p, c->lutMode, st));
+}
+
+// NHWC -> consumption order (NCHW flatten) into the scratch map in front of the first FC layer; *src: what the layer then reads
+hipError_t fc_input(QcnnCtx* c, int l, const Launch& L, const float** src) {
+  const LayerShape& s = c->shapes[l];
+  *src = L.src;
+  if (!s.hasDmap || L.flatFcInput) return hipSuccess;
+  float* flat = c->fcFlat + (size_t)L.p0 * fm_elems(c, l) * QCNN_PANEL;
+  *src = flat;
+  return qk_permute_rows(L.src, flat, arena_at<const int>(c, s.offDmap), (int)fm_elems(c, l), L.panels, L.live, L.st);
+}
+
+int launch_fc(QcnnCtx* c, int l, const Launch& L) {
+  LayerShape& s = c->shapes[l];
+  const int D = (int)fm_elems(c, l), Ct = c->dims[l + 1].c, panels = L.panels, relu = L.fuseRelu ? 1 : 0;
+  hipStream_t st = L.st;
+  if (!s.loaded) return fail(c, "layer %d: parameters not uploaded", l);
+  hipError_t e;
+  const float* src = nullptr;
+  if ((e = fc_input(c, l, L, &src)) != hipSuccess) return launched(c, l, e);
+  // precise path (CalcFeatMap_FCntPrec, src/CaffeEva.cc:932-966): a 1x1 conv on a 1x1 map
+  if (s.dense) return launch_dense(c, l, L, src, FmDims{1, 1, D}, FmDims{1, 1, Ct}, 1, 1, 0, 1);
+  // which panel kernel, and over how many workgroups its sub-space axis is split: the planner's rule (qk_choose_fc)
+  const QkFcGeom g = {D, Ct, s.M, s.K, s.Cs, s.P, panels, L.live};
+  const QkFcOptions o = {c->split, c->sym8, c->decode, c->lutMode, L.small ? 1 : 0, s.decKp < 0, s.tab[T_FC8].bytes != 0, fc_partial_left(c, L)};
+  const QkFcChoice ch = qk_choose_fc(g, o);
+  float* partial = ch.splits > 1 ? c->fcPartial + fc_partial_offset(c, L) : nullptr;
+  const size_t slab = (size_t)panels * Ct * QCNN_PANEL;
+  if (ch.family == QK_FC_DEC) {        // one-dim sub-spaces: decoded code words on the matrix pipe (qcnn_decoded.hip)
+    FcDecParams q;
+    q.src = src; q.dst = L.dst; q.partial = partial;
+    q.bias = arena_at<const float>(c, s.offBias);
+    q.wdec = arena_at<const float>(c, s.offDec);
+    q.D = D; q.Ct = Ct; q.S = s.decS;
+    q.relu = relu; q.panels = panels; q.halves = 2;
+    s.lastFrom = ch.family; s.lastZ = ch.splits;       // reported by qcnn_get_layer_split as (-3, k slices over workgroups)
+    e = qk_fc_dec(q, ch.splits, L.live, st);
+    if (e == hipSuccess && ch.splits > 1) e = qk_sum_partials(partial, L.dst, ch.splits, slab, relu, st);
+    return launched(c, l, e);
+  }
+  s.lastFrom = -1; s.lastZ = 1;
+  FcParams p;
+  p.src = src; p.dst = L.dst;
+  p.bias = arena_at<const float>(c, s.offBias);
+  p.ctrd = arena_at<const float>(c, s.offCtrd);
+  p.rows = arena_at<const uint8_t>(c, s.offAsmt);
+  p.cbn = c->packedFc ? reinterpret_cast<const uint8_t*>(table(c, s, T_CBN)) : nullptr;
+  p.cbnBits = s.cbnBits;
+  p.D = D; p.Ct = Ct; p.M = s.M; p.Cs = s.Cs; p.K = s.K; p.pd = s.P;
+  p.relu = relu; p.panels = panels;
+  p.msplit = 1; p.partial = nullptr;
+  if (s.P > 1) return launched(c, l, qk_fc_aprx(p, 0, st));     // pseudo sub-spaces: one pass of the exact-builder kernel
+  if (L.small && s.K % 4 == 0 && (size_t)L.live * s.M * s.K <= c->fcPartialElems) {
+    p.partial = c->fcPartial;          // few images: the tables are materialised in the partial-sum scratch
+    e = qk_fc_small(p, L.live, st);    // (K not a multiple of 4: the panel kernel below)
+    if (e != hipErrorInvalidValue) return launched(c, l, e);
+  }
+  p.msplit = ch.splits; p.partial = partial;
+  if (ch.family == QK_FC_WAVE12) {
+    e = qk_fc_aprx(p, c->lutMode, st);
+  } else {
+    s.lastFrom = ch.family; s.lastZ = ch.splits;   // reported by qcnn_get_layer_split as (-5 / -7 fp16 tables / -8 fp16 sums, splits of the sub-space axis)
+    const int mode = ch.family == QK_FC_SYM8 ? 0 : ch.family == QK_FC_SYM8_F16 ? 1 : 2;
+    const uint16_t* prog = mode ? ensure_f16_program(c, l, T_FC8, st) : table(c, s, T_FC8);
+    if (!prog) return 1;
+    e = qk_fc_sym8(p, prog, arena_at<const float>(c, s.offBook[BOOK_FC8]), st, mode);
+  }
+  if (e == hipSuccess && ch.splits > 1) e = qk_sum_partials(partial, L.dst, ch.splits, slab, relu, st);
+  return launched(c, l, e);
+}
+
+int launch_layer(QcnnCtx* c, int l, const Launch& L) {
+  const QcnnLayerDesc& d = c->layers[l];
+  const FmDims& a = c->dims[l];
+  const FmDims& b = c->dims[l + 1];
+  const size_t elems = (size_t)L.panels * fm_elems(c, l) * QCNN_PANEL;
+  switch (d.type) {
+    case QCNN_CONV: return launch_conv(c, l, L);
+    case QCNN_FCNT: return launch_fc(c, l, L);
+    case QCNN_POOL: return launched(c, l, qk_pool(L.src, L.dst, L.panels, a.h, a.w, a.c, b.h, b.w, d.knlSiz, d.stride, d.padSiz, L.live, L.st));
+    case QCNN_RELU: return launched(c, l, qk_relu(L.src, L.dst, elems, L.st));
+    case QCNN_LORN: return launched(c, l, qk_lrn(L.src, L.dst, L.panels, a.h * a.w, a.c, d.lrnSiz, d.lrnAlp, d.lrnBet, d.lrnIni, L.live, L.st));
+    case QCNN_DRPT:   // test-time dropout is a copy (src/CaffeEva.cc:1091-1096); only reached by qcnn_run_layer
+      return launched(c, l, hipMemcpyAsync(L.dst, L.src, elems * sizeof(float), hipMemcpyDeviceToDevice, L.st));
+    case QCNN_SMAX: return launched(c, l, qk_softmax(L.src, L.dst, L.panels, a.h * a.w * a.c, L.live, L.st));
+    default: return fail(c, "layer %d: invalid layer type %d", l, d.type);
+  }
 }
 
 // accumulate the recorded event pairs into the per-layer sums (blocks until the recorded work is done)
@@ -754,14 +750,6 @@ int drain_profile(QcnnCtx* c) {
   return 0;
 }
 
-// The layers of one forward.  The batch is cut into up to nStreams sub-batches of whole panels; sub-batch 0
-// runs on the context's stream, the others on auxiliary streams forked from / joined to it with events, so
-// that the LDS-bound conv/FC kernels of one sub-batch overlap the HBM-bound glue kernels of another and the
-// last dispatch round of one kernel is filled by the next.  Every image still sees exactly the same
-// arithmetic (panels are independent), so results do not depend on the number of streams.
-// Can the first layer's builders read the NCHW network input in place (no pack kernel, no packed copy of the input)?
-// Fast path only (layer-for-layer mode keeps fm[0] for dumps); a conv layer with <= 4 input channels per group (one
-// sub-space of <= 4 dims: exactly what the operand loads of one stage touch) and K = 128 or the exact builder.
 // workgroups a fused LRN + pool launch must have
 // (192: one panel of AlexNet's LRN1 + pool1 — 196 workgroups — fuses: 0.091 against 0.104 ms; LRN2 + pool2 at one / two panels —
 // 64 / 128 workgroups — must not: 0.21 against 0.065 ms)
@@ -774,6 +762,9 @@ int lrn_pool_min_blocks() {
 #endif
 }
 
+// Can the first layer's builders read the NCHW network input in place (no pack kernel, no packed copy of the input)?
+// Fast path only (layer-for-layer mode keeps fm[0] for dumps); a conv layer with <= 4 input channels per group (one
+// sub-space of <= 4 dims: exactly what the operand loads of one stage touch) and K = 128 or the exact builder.
 bool direct_input(const QcnnCtx* c, int n) {
   if (c->keepAll || c->L == 0 || c->layers[0].type != QCNN_CONV) return false;
   // the images of THIS forward inside 4 GiB: the in-place kernels keep image offsets in 32 bits
@@ -788,6 +779,11 @@ bool direct_input(const QcnnCtx* c, int n) {
   return c->inC / d.grpCnt <= 4 && (c->lutMode == 0 || c->shapes[0].K == 128);
 }
 
+// The layers of one forward.  The batch is cut into up to nStreams sub-batches of whole panels; sub-batch 0
+// runs on the context's stream, the others on auxiliary streams forked from / joined to it with events, so
+// that the LDS-bound conv/FC kernels of one sub-batch overlap the HBM-bound glue kernels of another and the
+// last dispatch round of one kernel is filled by the next.  Every image still sees exactly the same
+// arithmetic (panels are independent), so results do not depend on the number of streams.
 // pa / pb: the panels [pa, pb) of the batch this call runs (pb < 0: all of them) — a large host batch goes through in
 // chunks whose uploads overlap the previous chunk's layers, all chunks writing into the same whole-batch feature maps
 int run_layers(QcnnCtx* c, int n, const float* inNchw = nullptr, int pa = 0, int pb = -1) {
@@ -857,8 +853,11 @@ int run_layers(QcnnCtx* c, int n, const float* inNchw = nullptr, int pa = 0, int
         const hipError_t e = qk_lrn_pool(src, dst, p1 - p0, c->dims[l].h, c->dims[l].w, c->dims[l].c, c->dims[l + 2].h,
                                          c->dims[l + 2].w, d.lrnSiz, d.lrnAlp, d.lrnBet, d.lrnIni, live, st);
         if (e != hipSuccess) return fail(c, "layer %d (LRN + pool): %s", l, hipGetErrorString(e));
-      } else if (launch_layer(c, l, src, dst, p1 - p0, fuse, false, p0, st, direct ? inNchw : nullptr, n, live, small, k, ns, panels)) {
-        return 1;
+      } else {
+        Launch L = {src, dst, p1 - p0, p0, st};
+        L.inNchw = direct ? inNchw : nullptr; L.nImages = n; L.live = live; L.small = small;
+        L.sub = k; L.nsub = ns; L.panelsAll = panels; L.fuseRelu = fuse;
+        if (launch_layer(c, l, L)) return 1;
       }
       if (prof) {
         HIP_TRY(c, hipEventRecord(e1, st));
@@ -1420,7 +1419,7 @@ int qcnn_model_commit(QcnnCtx* c, int max_batch, void* dev_arena) {
     for (int l = 0; l < c->L; ++l)
       if (c->layers[l].type == QCNN_FCNT) maxCt = std::max<size_t>(maxCt, c->dims[l + 1].c);
     c->fcMaxCt = maxCt;
-    c->fcPartialElems = (size_t)kMaxFcSplit * c->maxPanels * maxCt * QCNN_PANEL;
+    c->fcPartialElems = (size_t)QK_MAX_FC_SPLIT * c->maxPanels * maxCt * QCNN_PANEL;
     if (c->fcPartialElems) HIP_TRY(c, hipMalloc(&c->fcPartial, c->fcPartialElems * sizeof(float)));
     if (c->firstFc >= 0 && c->shapes[c->firstFc].hasDmap)
       HIP_TRY(c, hipMalloc(&c->fcFlat, (size_t)c->maxPanels * fm_elems(c, c->firstFc) * QCNN_PANEL * sizeof(float) + kSlack));
@@ -1458,21 +1457,16 @@ int upload_bias_ctrd(QcnnCtx* c, int layer, const float* bias, const float* ctrd
   for (int m = 0; m < M; ++m)
     for (int k = 0; k < K; ++k)
       for (int dd = 0; dd < Cs; ++dd) ctrd[((size_t)m * Cs + dd) * K + k] = ctrd_file[((size_t)m * K + k) * Cs + dd];
-  std::vector<float> ctrdF;
-  if (s.progF8Bytes) {                // the eight-wave FC kernel's operand order (K = 32, Cs = 4)
-    ctrdF.resize((size_t)M * Cs * K);
+  // the eight-wave kernels' operand orders: FC (K = 32, Cs = 4) qk_ctrdf_index, conv (K = 128, Cs = 4 or 8) qk_ctrd8_index
+  std::vector<float> book[BOOK_COUNT];
+  for (int b = 0; b < BOOK_COUNT; ++b) {
+    if (!s.hasBook[b]) continue;
+    book[b].resize(ctrd.size());
     for (int m = 0; m < M; ++m)
       for (int dd = 0; dd < Cs; ++dd)
-        for (int k = 0; k < K; ++k) ctrdF[qk_ctrdf_index(m, dd, k)] = ctrd[((size_t)m * Cs + dd) * K + k];
-    HIP_TRY(c, hipMemcpyAsync(c->arena + s.offCtrdF, ctrdF.data(), ctrdF.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  std::vector<float> ctrd8;
-  if (s.prog8Bytes || s.prog8SBytes || s.progH8Bytes) {  // the eight-wave symmetric kernel's operand order (K = 128, Cs = 4 or 8)
-    ctrd8.resize((size_t)M * Cs * K);
-    for (int m = 0; m < M; ++m)
-      for (int dd = 0; dd < Cs; ++dd)
-        for (int k = 0; k < K; ++k) ctrd8[qk_ctrd8_index(m, dd, k, Cs / 4)] = ctrd[((size_t)m * Cs + dd) * K + k];
-    HIP_TRY(c, hipMemcpyAsync(c->arena + s.offCtrd8, ctrd8.data(), ctrd8.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        for (int k = 0; k < K; ++k)
+          book[b][b == BOOK_FC8 ? qk_ctrdf_index(m, dd, k) : qk_ctrd8_index(m, dd, k, Cs / 4)] = ctrd[((size_t)m * Cs + dd) * K + k];
+    HIP_TRY(c, hipMemcpyAsync(c->arena + s.offBook[b], book[b].data(), book[b].size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   }
   HIP_TRY(c, hipMemcpyAsync(c->arena + s.offBias, bias, sizeof(float) * Ct, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->arena + s.offCtrd, ctrd.data(), sizeof(float) * ctrd.size(), hipMemcpyHostToDevice, c->stream));
@@ -1482,91 +1476,39 @@ int upload_bias_ctrd(QcnnCtx* c, int layer, const float* bias, const float* ctrd
 }  // namespace
 
 namespace {
-// FC layer: the assignments (file order [Ct][M], 0-based code words) bit-packed exactly as a .cbn payload of `bits` bits per
-// element (include/FileIO.h:299-341: 4096-byte blocks of floor(32768 / bits) values, MSB first, no value across a block)
-// into the arena: the resident form the few-image kernel reads in place
+// FC layer: the assignments (file order [Ct][M], 0-based code words) bit-packed exactly as a .cbn payload of the layer's own
+// width (cbn_put) into the arena: the resident form the few-image kernel reads in place
 int upload_packed_assignments(QcnnCtx* c, int layer, const uint8_t* asmt_file) {
   const LayerShape& s = c->shapes[layer];
-  if (!s.cbnBytes) return 0;
+  if (!s.tab[T_CBN].bytes) return 0;
   const size_t n = (size_t)c->dims[layer + 1].c * s.M;
-  const int bits = s.cbnBits;
-  const size_t per = 4096 * 8 / (size_t)bits;
-  std::vector<uint8_t> blocks(s.cbnBytes, 0);
-  for (size_t e = 0; e < n; ++e) {
-    const size_t bit0 = (e % per) * bits;
-    uint8_t* b = blocks.data() + (e / per) * 4096 + (bit0 >> 3);
-    const unsigned w = (unsigned)asmt_file[e] << (16 - (bit0 & 7) - bits);      // <= 8 bits: at most two bytes
-    b[0] |= (uint8_t)(w >> 8);
-    if (w & 0xffu) b[1] |= (uint8_t)(w & 0xffu);
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->arena + s.offCbn, blocks.data(), blocks.size(), hipMemcpyHostToDevice, c->stream));
+  std::vector<uint8_t> blocks(s.tab[T_CBN].bytes, 0);
+  for (size_t e = 0; e < n; ++e) cbn_put(blocks.data(), e, s.cbnBits, asmt_file[e]);
+  HIP_TRY(c, hipMemcpyAsync(c->arena + s.tab[T_CBN].off, blocks.data(), blocks.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
-// rows table of a conv layer (already in the arena, same stream) -> program table
-hipError_t build_program(QcnnCtx* c, int layer, const QkSlots& sl) {
+// assignment rows of a layer (already in the arena, same stream) -> its decoded code words and every table of kTables it has
+hipError_t build_program(QcnnCtx* c, int layer) {
   const QcnnLayerDesc& d = c->layers[layer];
   const LayerShape& s = c->shapes[layer];
+  const TableGeom g = table_geom(c, layer);
+  const QkSlots& sl = g.sl;
+  const uint8_t* rows = arena_at<const uint8_t>(c, s.offAsmt);
+  const float* ctrd = arena_at<const float>(c, s.offCtrd);
+  const int Cin = c->dims[layer].c, Ct = c->dims[layer + 1].c;
   hipError_t e = hipSuccess;
   if (s.decKp < 0)                  // FC layer with one-dim sub-spaces
-    e = qk_decode_fc_weights(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<const float*>(c->arena + s.offCtrd),
-                             reinterpret_cast<float*>(c->arena + s.offDec), sl, (int)fm_elems(c, layer), s.K,
-                             c->dims[layer + 1].c, s.decS, c->stream);
+    e = qk_decode_fc_weights(rows, ctrd, arena_at<float>(c, s.offDec), sl, (int)fm_elems(c, layer), s.K, Ct, s.decS, c->stream);
   if (s.decKp > 0)                  // one sub-space of <= 4 dims: the code word every assignment names (qcnn_decoded.hip)
-    e = qk_decode_weights(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<const float*>(c->arena + s.offCtrd),
-                          reinterpret_cast<float*>(c->arena + s.offDec), sl, d.knlSiz, c->dims[layer].c, s.K,
-                          c->dims[layer + 1].c, s.decKp, s.decS, c->stream);
+    e = qk_decode_weights(rows, ctrd, arena_at<float>(c, s.offDec), sl, d.knlSiz, Cin, s.K, Ct, s.decKp, s.decS, c->stream);
   if (e == hipSuccess && s.decKp > 0 && s.decNV)
-    e = qk_decode_weights_nchw(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<const float*>(c->arena + s.offCtrd),
-                               reinterpret_cast<float*>(c->arena + s.offDecN), sl, d.knlSiz, c->dims[layer].c, s.K,
-                               c->dims[layer + 1].c, s.decNV, c->dims[layer + 1].c, c->stream);
+    e = qk_decode_weights_nchw(rows, ctrd, arena_at<float>(c, s.offDecN), sl, d.knlSiz, Cin, s.K, Ct, s.decNV, Ct, c->stream);
   if (e == hipSuccess && s.decKp > 0 && s.decNV && s.decBK)
-    e = qk_decode_weights_split(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<const float*>(c->arena + s.offCtrd),
-                                reinterpret_cast<uint16_t*>(c->arena + s.offDecB), sl, d.knlSiz, c->dims[layer].c, s.K,
-                                c->dims[layer + 1].c, s.decBK, c->stream);
-  if (e == hipSuccess && s.progF8Bytes)        // eight-wave FC kernel: uint16 offsets in its channel order
-    e = qk_build_program_fc8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<uint16_t*>(c->arena + s.offProgF8), sl,
-                             c->dims[layer + 1].c, s.M, c->stream);
-  if (e == hipSuccess && s.prog8Bytes) {       // eight-wave symmetric kernel: its own layout of the same table
-    const int Ct = c->dims[layer + 1].c;
-    e = qk_build_program8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<uint16_t*>(c->arena + s.offProg8), sl,
-                          qk_conv_sym8_config(c->dims[layer].c, d.grpCnt, Ct, s.M, s.Cs, s.K), Ct / d.grpCnt, d.grpCnt, d.knlSiz,
-                          d.stride, s.M, c->stream);
-  }
-  if (e == hipSuccess && s.progH8Bytes) {      // half-panel eight-wave kernel
-    const int Ct = c->dims[layer + 1].c;
-    e = qk_build_program_h8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<uint16_t*>(c->arena + s.offProgH8), sl,
-                            qk_conv_half8_config(c->dims[layer].c, d.grpCnt, Ct, s.M, s.Cs, s.K), Ct / d.grpCnt, d.grpCnt, d.knlSiz,
-                            d.stride, s.M, c->stream);
-  }
-  if (e == hipSuccess && s.progH8SBytes) {     // ... and its sliding form
-    const int Ct = c->dims[layer + 1].c;
-    e = qk_build_program_h8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<uint16_t*>(c->arena + s.offProgH8S), sl,
-                            qk_conv_half8_slide_config(c->dims[layer].c, d.grpCnt, Ct, s.M, s.Cs, s.K, d.knlSiz, d.stride), Ct / d.grpCnt,
-                            d.grpCnt, d.knlSiz, d.stride, s.M, c->stream);
-  }
-  if (e == hipSuccess && s.prog8SBytes) {      // ... and the program of its sliding form
-    const int Ct = c->dims[layer + 1].c;
-    e = qk_build_program8(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<uint16_t*>(c->arena + s.offProg8S), sl,
-                          qk_conv_sym8_slide_config(c->dims[layer].c, d.grpCnt, Ct, s.M, s.Cs, s.K, d.knlSiz, d.stride), Ct / d.grpCnt,
-                          d.grpCnt, d.knlSiz, d.stride, s.M, c->stream);
-  }
-  if (e == hipSuccess && s.progYBytes) {       // symmetric kernel: the (8 channels per wave, 2x2 tile) layout of the same table
-    const QkSlots s8 = qk_make_slots(sl.C, sl.groups, 8);
-    e = qk_build_program(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt), reinterpret_cast<uint16_t*>(c->arena + s.offProgY),
-                         sl, s8, qk_conv_program(s8, d.knlSiz, d.stride), d.knlSiz, d.stride, s.M, c->stream);
-  }
-  if (e != hipSuccess || !s.progBytes) return e;
-  e = qk_build_program(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt),
-                                  reinterpret_cast<uint16_t*>(c->arena + s.offProg), sl, sl,
-                                  qk_conv_program(sl, d.knlSiz, d.stride), d.knlSiz, d.stride, s.M, c->stream);
-  if (e == hipSuccess && s.progSBytes) {
-    const QkSlide sc = qk_slide_config(sl.C, sl.groups, d.knlSiz, d.stride);
-    e = qk_build_program(reinterpret_cast<const uint8_t*>(c->arena + s.offAsmt),
-                         reinterpret_cast<uint16_t*>(c->arena + s.offProgS), sl, sc.sl,
-                         qk_conv_program_slide(sc.sl, sc.ns, sc.nc, d.knlSiz, d.stride), d.knlSiz, d.stride, s.M, c->stream, 1);
-  }
+    e = qk_decode_weights_split(rows, ctrd, arena_at<uint16_t>(c, s.offDecB), sl, d.knlSiz, Cin, s.K, Ct, s.decBK, c->stream);
+  for (int k = 0; k < T_COUNT && e == hipSuccess; ++k)
+    if (s.tab[k].bytes && kTables[k].build) e = kTables[k].build(g, rows, arena_at<uint16_t>(c, s.tab[k].off), c->stream, 0);
   return e;
 }
 }  // namespace
@@ -1609,8 +1551,7 @@ int qcnn_model_set_layer_params(QcnnCtx* c, int layer, const float* bias, const 
   // with the channel axis in the order the gather waves consume it (QkSlots); padding entries point at slot 0.
   const int G = qcnn_stage_group(K);
   const size_t taps = (d.type == QCNN_CONV) ? (size_t)d.knlSiz * d.knlSiz : 1;
-  const int groups = (d.type == QCNN_CONV) ? d.grpCnt : 1;
-  const QkSlots sl = (d.type == QCNN_CONV) ? qk_conv_slots(Ct / groups, groups) : qk_fc_slots(Ct);
+  const QkSlots sl = table_geom(c, layer).sl;
   std::vector<uint8_t> asmt(s.asmtBytes + QCNN_ROWS_PAD, 0);
   for (int ch = 0; ch < Ct; ++ch) {
     const int entry = qk_slot_entry(sl, ch / sl.C, ch % sl.C);
@@ -1624,7 +1565,7 @@ int qcnn_model_set_layer_params(QcnnCtx* c, int layer, const float* bias, const 
   if (upload_bias_ctrd(c, layer, bias, ctrd_file)) return 1;
   if (upload_packed_assignments(c, layer, asmt_file)) return 1;
   HIP_TRY(c, hipMemcpyAsync(c->arena + s.offAsmt, asmt.data(), asmt.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, build_program(c, layer, sl));
+  HIP_TRY(c, build_program(c, layer));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   s.loaded = true;
   return 0;
@@ -1644,32 +1585,22 @@ int qcnn_model_set_layer_params_cbn(QcnnCtx* c, int layer, const float* bias, co
   const int Ct = c->dims[layer + 1].c;
   const size_t taps = (d.type == QCNN_CONV) ? (size_t)d.knlSiz * d.knlSiz : 1;
   if (s.P > 1) {                        // more than 128 code words: unpacked here, expanded into pseudo sub-spaces by the byte path
-    const size_t nF = (size_t)Ct * taps * s.Mfile, perF = 4096 * 8 / (size_t)bits;
-    if (cbn_bytes < (nF + perF - 1) / perF * 4096) return fail(c, "layer %d: %zu bytes of packed assignments, %zu needed", layer, cbn_bytes, (nF + perF - 1) / perF * 4096);
+    const size_t nF = (size_t)Ct * taps * s.Mfile;
+    if (cbn_bytes < cbn_size(nF, bits)) return fail(c, "layer %d: %zu bytes of packed assignments, %zu needed", layer, cbn_bytes, cbn_size(nF, bits));
     std::vector<uint8_t> vals(nF);
-    for (size_t e = 0; e < nF; ++e) {
-      const size_t bit0 = (e % perF) * bits;
-      const uint8_t* b = cbn_blocks + (e / perF) * 4096 + (bit0 >> 3);
-      const unsigned w = ((unsigned)b[0] << 8) | (unsigned)b[(bit0 & 7) + bits > 8 ? 1 : 0];
-      vals[e] = (uint8_t)((w >> (16 - (bit0 & 7) - bits)) & ((1u << bits) - 1u));
-    }
+    for (size_t e = 0; e < nF; ++e) vals[e] = (uint8_t)cbn_get(cbn_blocks, e, bits);
     return qcnn_model_set_layer_params(c, layer, bias, ctrd_file, vals.data());
   }
-  const int groups = (d.type == QCNN_CONV) ? d.grpCnt : 1;
-  const QkSlots sl = (d.type == QCNN_CONV) ? qk_conv_slots(Ct / groups, groups) : qk_fc_slots(Ct);
+  const QkSlots sl = table_geom(c, layer).sl;
   const size_t n = (size_t)Ct * taps * s.M;
-  const size_t per = 4096 * 8 / (size_t)bits;
-  const size_t need = (n + per - 1) / per * 4096;
+  const size_t need = cbn_size(n, bits);
   if (cbn_bytes < need) return fail(c, "layer %d: %zu bytes of packed assignments, %zu needed", layer, cbn_bytes, need);
   if (upload_bias_ctrd(c, layer, bias, ctrd_file)) return 1;
-  if (s.cbnBytes && bits != s.cbnBits) {           // a stream of another width: re-packed at the layer's own width for the resident copy
+  if (s.tab[T_CBN].bytes && bits != s.cbnBits) {           // a stream of another width: re-packed at the layer's own width for the resident copy
     std::vector<uint8_t> vals(n);
     bool bad = false;
     for (size_t e = 0; e < n; ++e) {
-      const size_t bit0 = (e % per) * bits;
-      const uint8_t* b = cbn_blocks + (e / per) * 4096 + (bit0 >> 3);
-      const unsigned w = ((unsigned)b[0] << 8) | (unsigned)b[(bit0 & 7) + bits > 8 ? 1 : 0];
-      vals[e] = (uint8_t)((w >> (16 - (bit0 & 7) - bits)) & ((1u << bits) - 1u));
+      vals[e] = (uint8_t)cbn_get(cbn_blocks, e, bits);
       bad = bad || vals[e] >= s.K;
     }
     if (bad) return fail(c, "layer %d: an assignment >= K = %d in the packed stream", layer, s.K);
@@ -1680,13 +1611,13 @@ int qcnn_model_set_layer_params_cbn(QcnnCtx* c, int layer, const float* bias, co
   HIP_TRY(c, hipMalloc(&dev, need + sizeof(int)));
   bad = reinterpret_cast<int*>(dev + need);
   hipError_t e = hipMemcpyAsync(dev, cbn_blocks, need, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && s.cbnBytes && bits == s.cbnBits)       // the payload itself is the resident packed form
-    e = hipMemcpyAsync(c->arena + s.offCbn, dev, std::min(need, s.cbnBytes), hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess && s.tab[T_CBN].bytes && bits == s.cbnBits)       // the payload itself is the resident packed form
+    e = hipMemcpyAsync(c->arena + s.tab[T_CBN].off, dev, std::min(need, s.tab[T_CBN].bytes), hipMemcpyDeviceToDevice, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(c->arena + s.offAsmt, 0, s.asmtBytes + QCNN_ROWS_PAD, c->stream);   // padding entries -> row 0
   if (e == hipSuccess)
     e = qk_decode_cbn(dev, bits, n, Ct, (int)taps, s.M, s.K, sl, reinterpret_cast<uint8_t*>(c->arena + s.offAsmt), bad, c->stream);
-  if (e == hipSuccess) e = build_program(c, layer, sl);
+  if (e == hipSuccess) e = build_program(c, layer);
   int flag = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(&flag, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1990,7 +1921,9 @@ int qcnn_run_layer(QcnnCtx* c, int layer, const float* in_host, int n, float* ou
   HIP_TRY(c, hipMemcpyAsync(c->stageIn, in_host, (size_t)n * Ein * sizeof(float), hipMemcpyHostToDevice, c->stream));
   hipError_t e = qk_pack_rows(c->stageIn, src, n, Ein, c->stream);
   if (e != hipSuccess) return fail(c, "pack launch failed: %s", hipGetErrorString(e));
-  if (launch_layer(c, layer, src, dst, panels, false, true, 0, c->stream)) return 1;
+  Launch L = {src, dst, panels, 0, c->stream};
+  L.flatFcInput = true;
+  if (launch_layer(c, layer, L)) return 1;
   e = qk_unpack_rows(dst, c->stageOut, n, Eout, c->stream);
   if (e != hipSuccess) return fail(c, "unpack launch failed: %s", hipGetErrorString(e));
   HIP_TRY(c, hipMemcpyAsync(out_host, c->stageOut, (size_t)n * Eout * sizeof(float), hipMemcpyDeviceToHost, c->stream));

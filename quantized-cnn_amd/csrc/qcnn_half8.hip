@@ -44,7 +44,6 @@
 
 namespace {
 
-constexpr int NW8 = 8;                              // waves per workgroup (2 per SIMD: 256 registers each)
 constexpr uint32_t HSTAGE = 4u * TILEB;             // a stage: four image tiles = 32 KB
 constexpr uint32_t PROGH_LDS = 2u * HSTAGE;         // three program-row buffers behind the two LUT stages
 constexpr uint32_t PROGH_BUF = 3072u;

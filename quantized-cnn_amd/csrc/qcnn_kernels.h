@@ -30,6 +30,9 @@
 #define QCNN_TILE_BYTES 8192   // one image tile of a stage: 128 rows x 16 images x 4 B
 #define QCNN_STAGE_BYTES (8 * QCNN_TILE_BYTES)
 #define QCNN_GATHER_WAVES 12   // gather waves of a conv/FC workgroup (of 16; the other four build the stages)
+constexpr int NW8 = 8;                              // waves of an eight-wave workgroup (qcnn_sym8.hip, qcnn_half8.hip; 2 per SIMD: 256 registers each)
+constexpr int FC8_CPW = 96;                         // k_fc_sym8: channels per wave (192 accumulator registers)
+constexpr int FC8_SUBB = NW8 * 2 * (FC8_CPW / 2) * 2;   // ... program bytes of one sub-space for the workgroup: 16 x 48 uint16 = 1536
 
 // A LUT stage holds G = qcnn_stage_group(K) consecutive sub-spaces of one source pixel (conv) / of the
 // input vector (FC): G * K <= 128 rows;  stage row of a code word = (m % G) * K + assignment  (< 128).
@@ -333,7 +336,6 @@ hipError_t qk_dense(const DenseParams& p, hipStream_t st);
 // fp16-storage kernels of qcnn_sym8.hip do not cover).  Return hipError_t of the launch.
 hipError_t qk_conv_aprx(const ConvParams& p, int lutMode, hipStream_t st);
 hipError_t qk_fc_aprx(const FcParams& p, int lutMode, hipStream_t st);
-int qk_fc_channels_per_block(int Ct);   // output channels one k_fc_aprx workgroup covers
 // The same two layers for a batch of a few images (qcnn_small.hip): lanes = output channels, one workgroup per (output
 // tile, channel chunk, image); n = images of the launch (all inside the panels src/dst point at); f32 arithmetic,
 // results equal to the panel kernels' to rounding.  p.rows / p.ctrd / p.bias as above; msplit / partial unused.

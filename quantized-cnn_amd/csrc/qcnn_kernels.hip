@@ -1529,8 +1529,6 @@ hipError_t qk_conv_aprx(const ConvParams& pIn, int lutMode, hipStream_t st) {
   }
 }
 
-int qk_fc_channels_per_block(int Ct) { return NGW * qk_fc_slots(Ct).cpw; }
-
 // p.msplit is chosen by the caller (engine): 1 keeps the reference's summation order.
 hipError_t qk_fc_aprx(const FcParams& pIn, int lutMode, hipStream_t st) {
   FcParams p = pIn;

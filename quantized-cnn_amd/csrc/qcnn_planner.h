@@ -1,4 +1,4 @@
-// qcnn_planner.h — the launch planner of the conv table kernels (host side, no device code): which kernel family runs a conv
+// qcnn_planner.h — the launch planner of the conv and FC table kernels (host side, no device code): which kernel family runs a
 // launch of a given geometry and panel count, and how it is cut.
 //
 // Every family has a cost model in the same unit — "stage-times" = LUT stages of the 16-wave tile kernel (~2500 cycles), tiles /
@@ -56,5 +56,22 @@ constexpr double QK_HALF8_SLIDE_FACTOR = 1.25;  // ... of the half-panel sliding
 
 QkConvPlan qk_plan_conv(const ConvParams& p, const QkPlanOptions& o);
 QkConvChoice qk_choose_conv(const QkConvPlan& pl, const QkPlanOptions& o);
+
+// FC layers: which panel kernel runs a launch and over how many workgroups its sub-space (decoded form: k) axis is split.
+constexpr int QK_MAX_FC_SPLIT = 32;       // workgroups along the sub-space axis of an FC layer (partial sums reduced in fixed order)
+struct QkFcGeom {
+  int D, Ct, M, K, Cs, P;                 // as the kernels see the layer (FcParams; P = FcParams::pd)
+  int panels, live;                       // of this launch: panels, images per panel
+};
+struct QkFcOptions {
+  int split, sym8, decode, lutMode;       // QCNN_OPT_SPLIT / _SYM8 / _DECODE / _LUT_MODE as set
+  int small;                              // the forward runs the few-image kernels (the eight-wave form stays out of their way)
+  int hasDec, hasSym8;                    // forms the layer's arena holds: decoded code words, the eight-wave program table
+  size_t scratchFloats;                   // partial-sum scratch this sub-batch's slab leaves
+};
+// family codes = what qcnn_get_layer_split reports as *tiles_unsplit for an FC layer
+enum QkFcFamily { QK_FC_WAVE12 = -1, QK_FC_DEC = -3, QK_FC_SYM8 = -5, QK_FC_SYM8_F16 = -7, QK_FC_SYM8_F16SUM = -8 };
+struct QkFcChoice { int family, splits; };
+QkFcChoice qk_choose_fc(const QkFcGeom& g, const QkFcOptions& o);
 
 #endif  // QCNN_PLANNER_H_

@@ -148,6 +148,23 @@ QkH8Config qk_conv_half8_slide_config(int Cin, int grp, int Ct, int M, int Cs, i
 // ------------------------------------------------------------------------------------------------------------------
 // cost models
 // ------------------------------------------------------------------------------------------------------------------
+// source pixels (rows x columns, clipped to the map) the TH x TW output tile of rank r looks at
+static int tile_pixels(const ConvParams& p, int r, int tilesY, int tilesX, int TH, int TW) {
+  int ty, tx;
+  tile_of_rank(r, tilesY, tilesX, ty, tx);
+  const int ho0 = ty * TH, wo0 = tx * TW;
+  const int hoL = std::min(ho0 + TH, p.Ho) - 1, woL = std::min(wo0 + TW, p.Wo) - 1;
+  const int rows = std::min(p.H - 1, hoL * p.stride - p.pad + p.knl - 1) - std::max(0, ho0 * p.stride - p.pad) + 1;
+  const int cols = std::min(p.W - 1, woL * p.stride - p.pad + p.knl - 1) - std::max(0, wo0 * p.stride - p.pad) + 1;
+  return std::max(rows, 0) * std::max(cols, 0);
+}
+// border-clipped taps along one axis, summed over its n output positions (nIn input positions)
+static double clipped_taps(const ConvParams& p, int n, int nIn) {
+  long long t = 0;
+  for (int o = 0; o < n; ++o) t += std::min(p.knl - 1, nIn - 1 - (o * p.stride - p.pad)) - std::max(0, -(o * p.stride - p.pad)) + 1;
+  return (double)t;
+}
+
 // predicted duration (in stage-times, like QkSplitPlan::cost) of the symmetric kernel for a launch over p.panels panels:
 // 2x2 tiles, list-scheduled heaviest first on 256 CUs
 double qk_conv_sym_cost(const ConvParams& p) {
@@ -155,16 +172,10 @@ double qk_conv_sym_cost(const ConvParams& p) {
   std::vector<double> cu(256, 0.0);
   std::vector<double> cost((size_t)tiles);
   for (int r = 0; r < tiles; ++r) {
-    int ty, tx;
-    tile_of_rank(r, tilesY, tilesX, ty, tx);
-    const int ho0 = ty * 2, wo0 = tx * 2;
-    const int hoL = std::min(ho0 + 2, p.Ho) - 1, woL = std::min(wo0 + 2, p.Wo) - 1;
-    const int rows = std::min(p.H - 1, hoL * p.stride - p.pad + p.knl - 1) - std::max(0, ho0 * p.stride - p.pad) + 1;
-    const int cols = std::min(p.W - 1, woL * p.stride - p.pad + p.knl - 1) - std::max(0, wo0 * p.stride - p.pad) + 1;
     // a symmetric stage serves a quarter more look-ups than the 1x3 tile's and takes longer; the factor is calibrated on
     // AlexNet conv2 so that the planner's choice matches the measurements (1000 / 500 / 250 images: symmetric -5.9 / -4.2 /
     // -2.0 %, 125 images: +17 %)
-    cost[r] = 1.09 * ((double)std::max(rows, 0) * std::max(cols, 0) * p.M) + 10.0;
+    cost[r] = 1.09 * ((double)tile_pixels(p, r, tilesY, tilesX, 2, 2) * p.M) + 10.0;
   }
   const long long wgs = (long long)tiles * p.panels * p.grp;
   if (wgs >= 8 * 256) {
@@ -204,28 +215,12 @@ QkSplitPlan qk_conv_plan(const ConvParams& p, size_t scratchFloats) {
   if ((long long)tiles * p.panels * ny >= 8 * 256) {                     // enough workgroups for the tail not to matter
     double stages = 0.0;
     const int G0 = qcnn_stage_group(p.K), MG0 = (p.M + G0 - 1) / G0;
-    for (int r = 0; r < tiles; ++r) {
-      int ty, tx;
-      tile_of_rank(r, tilesY, tilesX, ty, tx);
-      const int ho0 = ty * TH, wo0 = tx * TW;
-      const int hoL = std::min(ho0 + TH, p.Ho) - 1, woL = std::min(wo0 + TW, p.Wo) - 1;
-      const int rows = std::min(p.H - 1, hoL * p.stride - p.pad + p.knl - 1) - std::max(0, ho0 * p.stride - p.pad) + 1;
-      const int cols = std::min(p.W - 1, woL * p.stride - p.pad + p.knl - 1) - std::max(0, wo0 * p.stride - p.pad) + 1;
-      stages += (double)std::max(rows, 0) * std::max(cols, 0) * MG0 + 10.0;
-    }
+    for (int r = 0; r < tiles; ++r) stages += (double)tile_pixels(p, r, tilesY, tilesX, TH, TW) * MG0 + 10.0;
     none.cost = stages * p.panels * ny / 256.0;
     return none;
   }
   std::vector<int> S(tiles);
-  for (int r = 0; r < tiles; ++r) {
-    int ty, tx;
-    tile_of_rank(r, tilesY, tilesX, ty, tx);
-    const int ho0 = ty * TH, wo0 = tx * TW;
-    const int hoL = std::min(ho0 + TH, p.Ho) - 1, woL = std::min(wo0 + TW, p.Wo) - 1;
-    const int rows = std::min(p.H - 1, hoL * p.stride - p.pad + p.knl - 1) - std::max(0, ho0 * p.stride - p.pad) + 1;
-    const int cols = std::min(p.W - 1, woL * p.stride - p.pad + p.knl - 1) - std::max(0, wo0 * p.stride - p.pad) + 1;
-    S[r] = std::max(rows, 0) * std::max(cols, 0) * MG;
-  }
+  for (int r = 0; r < tiles; ++r) S[r] = tile_pixels(p, r, tilesY, tilesX, TH, TW) * MG;
   const double kFixed = 10.0;          // stage-times a workgroup spends outside its stage loop (roles, first stage, stores)
   const double kStageUs = 1.1;         // ~2700 cycles
   std::vector<double> cu(256);
@@ -392,22 +387,11 @@ double qk_conv_sym8_cost(const ConvParams& p, const Qk8Config& cf, double scale,
   std::vector<double> stages((size_t)tiles);
   double total = 0.0;
   for (int r = 0; r < tiles; ++r) {
-    int ty, tx;
-    tile_of_rank(r, tilesY, tilesX, ty, tx);
-    const int ho0 = ty * TH, wo0 = tx * TW;
-    const int hoL = std::min(ho0 + TH, p.Ho) - 1, woL = std::min(wo0 + TW, p.Wo) - 1;
-    const int rows = std::min(p.H - 1, hoL * p.stride - p.pad + p.knl - 1) - std::max(0, ho0 * p.stride - p.pad) + 1;
-    const int cols = std::min(p.W - 1, woL * p.stride - p.pad + p.knl - 1) - std::max(0, wo0 * p.stride - p.pad) + 1;
-    stages[r] = (double)std::max(rows, 0) * std::max(cols, 0) * p.M;
+    stages[r] = (double)tile_pixels(p, r, tilesY, tilesX, TH, TW) * p.M;
     total += stages[r];
   }
   // row look-ups of one group and channel chunk per panel (border-clipped taps x sub-spaces x channels) per built stage
-  auto taps = [&](int n, int nIn) {
-    long long t = 0;
-    for (int o = 0; o < n; ++o) t += std::min(p.knl - 1, nIn - 1 - (o * p.stride - p.pad)) - std::max(0, -(o * p.stride - p.pad)) + 1;
-    return (double)t;
-  };
-  const double perStage = total > 0.0 ? taps(p.Ho, p.H) * taps(p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, 8 * cf.cpw) / total : 0.0;
+  const double perStage = total > 0.0 ? clipped_taps(p, p.Ho, p.H) * clipped_taps(p, p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, 8 * cf.cpw) / total : 0.0;
   const double factor = scale * (2540.0 + 1.97 * perStage) / 2500.0;
   const int ny = p.grp * cf.chunks;
   const long long wgs = (long long)tiles * p.panels * ny;
@@ -448,12 +432,7 @@ double qk_conv_sym8_slide_plan(ConvParams& p, const Qk8Config& cf, double scale)
     const int rows = std::min(p.H - 1, (b - 1) * p.stride - p.pad + p.knl - 1) - std::max(0, a * p.stride - p.pad) + 1;
     return (double)std::max(rows, 0) * std::max(cols, 0) * p.M;
   };
-  auto taps = [&](int n, int nIn) {
-    long long t = 0;
-    for (int o = 0; o < n; ++o) t += std::min(p.knl - 1, nIn - 1 - (o * p.stride - p.pad)) - std::max(0, -(o * p.stride - p.pad)) + 1;
-    return (double)t;
-  };
-  const double lookups = taps(p.Ho, p.H) * taps(p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, 8 * cf.cpw);   // per group, chunk and panel
+  const double lookups = clipped_taps(p, p.Ho, p.H) * clipped_taps(p, p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, 8 * cf.cpw);   // per group, chunk and panel
   std::vector<std::vector<int> > cands;
   for (int n = 1; n <= 4 && n * ns <= p.Ho; ++n) {
     std::vector<int> b(n + 1);
@@ -519,22 +498,11 @@ double qk_conv_half8_cost(const ConvParams& p, const QkH8Config& cf, double scal
   std::vector<double> stages((size_t)tiles);
   double total = 0.0;
   for (int r = 0; r < tiles; ++r) {
-    int ty, tx;
-    tile_of_rank(r, tilesY, tilesX, ty, tx);
-    const int ho0 = ty * TH, wo0 = tx * TW;
-    const int hoL = std::min(ho0 + TH, p.Ho) - 1, woL = std::min(wo0 + TW, p.Wo) - 1;
-    const int rows = std::min(p.H - 1, hoL * p.stride - p.pad + p.knl - 1) - std::max(0, ho0 * p.stride - p.pad) + 1;
-    const int cols = std::min(p.W - 1, woL * p.stride - p.pad + p.knl - 1) - std::max(0, wo0 * p.stride - p.pad) + 1;
-    stages[r] = (double)std::max(rows, 0) * std::max(cols, 0) * p.M;
+    stages[r] = (double)tile_pixels(p, r, tilesY, tilesX, TH, TW) * p.M;
     total += stages[r];
   }
-  auto taps = [&](int n, int nIn) {
-    long long t = 0;
-    for (int o = 0; o < n; ++o) t += std::min(p.knl - 1, nIn - 1 - (o * p.stride - p.pad)) - std::max(0, -(o * p.stride - p.pad)) + 1;
-    return (double)t;
-  };
   // row look-ups (of 64 images) of one group and channel chunk per half panel and built stage
-  const double perStage = total > 0.0 ? taps(p.Ho, p.H) * taps(p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, (8 / cf.ws) * cf.cpw) / total : 0.0;
+  const double perStage = total > 0.0 ? clipped_taps(p, p.Ho, p.H) * clipped_taps(p, p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, (8 / cf.ws) * cf.cpw) / total : 0.0;
   // (two wave sets: a stage's valid positions rarely split evenly over the sets, and the slower set holds the barrier)
   const double factor = scale * (cf.ws == 2 ? QK_HALF8_TWO_SETS : 1.0) * (QK_HALF8_FIX + QK_HALF8_PER_ROW * perStage) / 2500.0;
   const int ny = p.grp * cf.chunks;
@@ -572,12 +540,7 @@ double qk_conv_half8_slide_plan(ConvParams& p, const QkH8Config& cf, double scal
     const int rows = std::min(p.H - 1, (b - 1) * p.stride - p.pad + p.knl - 1) - std::max(0, a * p.stride - p.pad) + 1;
     return (double)std::max(rows, 0) * std::max(cols, 0) * p.M;
   };
-  auto taps = [&](int n, int nIn) {
-    long long t = 0;
-    for (int o = 0; o < n; ++o) t += std::min(p.knl - 1, nIn - 1 - (o * p.stride - p.pad)) - std::max(0, -(o * p.stride - p.pad)) + 1;
-    return (double)t;
-  };
-  const double lookups = taps(p.Ho, p.H) * taps(p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, (8 / cf.ws) * cf.cpw);   // per group, chunk and half panel
+  const double lookups = clipped_taps(p, p.Ho, p.H) * clipped_taps(p, p.Wo, p.W) * p.M * std::min(p.Ct / p.grp, (8 / cf.ws) * cf.cpw);   // per group, chunk and half panel
   std::vector<std::vector<int> > cands;
   for (int n = 1; n <= 4 && n * ns <= p.Ho; ++n) {
     std::vector<int> b(n + 1);
@@ -730,6 +693,109 @@ QkConvChoice qk_choose_conv(const QkConvPlan& pl, const QkPlanOptions& o) {
   if (pl.segN > 0) { ch.family = QK_FAM_SLIDE16; segs(pl.segN, pl.segBeg); return ch; }
   if (pl.plan.Z > 1) { ch.splitFrom = pl.plan.splitFrom; ch.Z = pl.plan.Z; }
   return ch;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// FC layers: geometry of the panel kernels (qk_fc_aprx, qk_fc_sym8, qk_fc_dec) and the decision which one runs a launch
+// ------------------------------------------------------------------------------------------------------------------
+bool qk_fc_sym8_shape(int D, int Ct, int M, int Cs, int K) {
+  return K == 32 && Cs == 4 && M % 4 == 0 && D == 4 * M && Ct >= 2 * FC8_CPW && Ct % 2 == 0;
+}
+int qk_fc_sym8_chunks(int Ct) { return (Ct + NW8 * FC8_CPW - 1) / (NW8 * FC8_CPW); }
+size_t qk_fc_sym8_program_bytes(int Ct, int M) { return (size_t)M * qk_fc_sym8_chunks(Ct) * FC8_SUBB; }
+
+bool qk_fc_dec_shape(int D, int M, int Cs, int Ct, int* S) {
+  if (Cs != 1 || M != D || D % 64 || Ct < 1) return false;
+  if ((size_t)D * QCNN_PANEL * sizeof(float) >= (1ull << 32)) return false;
+  *S = (Ct + 63) / 64 * 64;
+  return (size_t)D * *S * sizeof(float) < (1ull << 32);
+}
+
+int qk_fc_dec_slices(int D, int Ct, int panels, int live) {
+  // k slices over workgroups: until the launch has about a workgroup per CU, every wave keeping >= 4 steps
+  const int wgs = ((Ct + 63) / 64) * panels * ((live + 63) / 64);
+  int z = 1;
+  while (wgs * z < 192 && D % (64 * 2 * z) == 0 && D / (64 * 2 * z) >= 4 && 2 * z <= 32) z *= 2;   // <= 32 slabs of scratch per sub-batch
+  return z;
+}
+
+QkFcChoice qk_choose_fc(const QkFcGeom& g, const QkFcOptions& o) {
+  const auto fits = [&](int z) { return (size_t)z * g.panels * g.Ct * QCNN_PANEL <= o.scratchFloats; };
+  // one-dim sub-spaces: decoded code words on the matrix pipe (qcnn_decoded.hip).  The f32 MFMA mode only: the exact builder
+  // keeps the reference's summation order and the fp16 study is about the tables themselves.
+  if (o.decode && o.hasDec && o.lutMode == 1) {
+    // k slices over workgroups change the summation order with the panel count of the launch: QCNN_OPT_SPLIT only (off =
+    // batch-size-invariant bits, as for the split conv tiles and the per-launch FC split below)
+    const int z = o.split ? std::min(qk_fc_dec_slices(g.D, g.Ct, g.panels, g.live), QK_MAX_FC_SPLIT) : 1;
+    return {QK_FC_DEC, z > 1 && fits(z) ? z : 1};
+  }
+  // pseudo sub-spaces and the exact builder keep one pass so that the summation order stays the reference's
+  if (g.P > 1 || o.lutMode < 1) return {QK_FC_WAVE12, 1};
+  // k_fc_sym8: 768 channels per workgroup.  A launch of one or two panels stays with the 12-wave kernel's 384 (measured,
+  // AlexNet fc6 / fc7 per 125 images: 0.092 / 0.053 against 0.108 / 0.070 ms; 250: 0.148 / 0.076 against 0.150 / 0.082; 500:
+  // 0.304 / 0.135 against 0.259 / 0.129) — under QCNN_OPT_SPLIT only, whose results may depend on the batch size
+  const bool fc8h = o.hasSym8 && o.sym8 && o.lutMode >= 2 && !o.small;      // fp16 table storage (3: fp16 sums too): always the eight-wave form
+  const bool fc8 = fc8h || (o.hasSym8 && o.sym8 && o.lutMode == 1 && !o.small && (o.sym8 >= 2 || !o.split || g.panels >= 3));
+  // Split the sub-space axis over workgroups when the (channel chunk x panel) grid cannot fill the chip.
+  const int G = qcnn_stage_group(g.K);
+  const int stages = (g.M + G - 1) / G;
+  // batch-independent choice (a given image must produce the same bits in any batch): the split count
+  // that fills 256 CUs best at the design point of 8 panels (1000 images) while every workgroup keeps
+  // >= 24 stages (>= 12 when that leaves a single panel — one GPU's share of a sharded batch — on fewer than 64
+  // CUs); ties go to fewer splits.  (A grid of chunks x splits x panels workgroups runs in
+  // ceil(grid / 256) rounds: 528 workgroups cost as much as 768.)
+  const int cpb = QCNN_GATHER_WAVES * qk_fc_slots(g.Ct).cpw;     // output channels one k_fc_aprx workgroup covers
+  const int chunks = fc8 ? qk_fc_sym8_chunks(g.Ct) : (g.Ct + cpb - 1) / cpb;
+  auto pick = [&](int minStages) {
+    int best = 1;
+    double bestFill = 0.0;
+    for (int cand = 1; cand <= QK_MAX_FC_SPLIT; ++cand) {
+      if (cand > 1 && stages / cand < minStages) break;
+      const int grid = chunks * cand * 8;
+      const double fill = (double)grid / (256.0 * ((grid + 255) / 256));
+      if (fill > bestFill + 1e-9) { bestFill = fill; best = cand; }
+    }
+    return best;
+  };
+  int ms = pick(24);
+  if (chunks * ms < 64) ms = pick(12);     // few channel chunks (a 1000-way classifier): a single panel would sit on < 64 CUs
+  if (o.split && chunks * ms * g.panels < 2 * 256) {
+    // QCNN_OPT_SPLIT: a launch of a few panels (one GPU's share of a sharded batch) picks the split for ITS panel
+    // count (the bits of an image then depend on the batch size, to rounding): >= 8 stages per workgroup, fewest
+    // rounds of 256 workgroups x stages each, ties to fewer splits
+    int best = ms;
+    double bestT = 1e30;
+    for (int cand = 1; cand <= QK_MAX_FC_SPLIT; ++cand) {
+      if (cand > 1 && stages / cand < 8) break;
+      const int grid = chunks * cand * g.panels;
+      const double t = (double)((grid + 255) / 256) * ((double)((stages + cand - 1) / cand) + 10.0) + 0.5 * cand;
+      if (t < bestT - 1e-9) { bestT = t; best = cand; }
+    }
+    ms = best;
+  }
+  if (!fits(ms)) ms = 1;
+  if (!fc8) return {QK_FC_WAVE12, ms};
+  // every workgroup along the sub-space axis needs a stage: the count qk_fc_sym8 will accept for this split
+  const int stagesF = g.M / 4, per = (stagesF + ms - 1) / ms;
+  return {fc8h ? (o.lutMode == 3 ? QK_FC_SYM8_F16SUM : QK_FC_SYM8_F16) : QK_FC_SYM8, (stagesF + per - 1) / per};
+}
+
+// Diagnostic / test entry (extern "C", plain ints): the choice for one FC launch.
+//   geom[8] = D, Ct, M, K, Cs, P, panels, live            (M, K as the kernels see them: P pseudo sub-spaces per sub-space of the file)
+//   opts[7] = split, sym8, decode, lutMode, small, flatten (1: the input is a map the layer reads NCHW-flattened), scratch floats (< 0: ample)
+// The forms a layer would have are derived from its shape exactly as qcnn_model_commit plans them.
+//   choice[2] = family (QkFcFamily), splits
+extern "C" int qcnn_plan_fc_query(const int* geom, const int* opts, int* choice) {
+  if (!geom || !opts || !choice) return 1;
+  const QkFcGeom g = {geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], geom[6], geom[7]};
+  if (g.D < 1 || g.Ct < 1 || g.M < 1 || g.K < 1 || g.K > QCNN_MAX_K || g.Cs < 1 || g.P < 1 || g.panels < 1 || g.live < 1 || g.live > QCNN_PANEL) return 1;
+  QkFcOptions o = {opts[0], opts[1], opts[2], opts[3], opts[4], 0, 0, opts[6] < 0 ? ~(size_t)0 : (size_t)opts[6]};
+  int S = 0;
+  o.hasSym8 = g.P == 1 && qk_fc_sym8_shape(g.D, g.Ct, g.M, g.Cs, g.K);
+  o.hasDec = !opts[5] && qk_fc_dec_shape(g.D, g.M, g.Cs, g.Ct, &S);
+  const QkFcChoice ch = qk_choose_fc(g, o);
+  choice[0] = ch.family; choice[1] = ch.splits;
+  return 0;
 }
 
 // Diagnostic / test entry (extern "C", plain ints): the plan and the choice for one conv launch.

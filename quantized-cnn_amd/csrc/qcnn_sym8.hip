@@ -76,7 +76,6 @@ extern "C" int qcnn_debug_trace8_read(unsigned long long* host, int block) {
 
 namespace {
 
-constexpr int NW8 = 8;                              // waves per workgroup (2 per SIMD: 256 registers each)
 constexpr uint32_t PROG8_LDS = 2u * STAGE_BYTES;    // three program-row buffers behind the two LUT stages
 constexpr uint32_t PROG8_BUF = 2048u;
 
@@ -621,8 +620,6 @@ __global__ __launch_bounds__(NW8 * 64) void k_conv_sym8(ConvParams p, int tilesX
 // K = 32, Cs = 4, M a multiple of 4, D = 4 M (AlexNet / VGG-16 fc6, fc7); everything else stays with k_fc_aprx.
 // Stage loop, barriers and add-TID stores as in k_conv_sym8; the sub-space axis is split over blockIdx.z like k_fc_aprx's.
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int FC8_CPW = 96;                               // channels per wave (192 accumulator registers)
-constexpr int FC8_SUBB = NW8 * 2 * (FC8_CPW / 2) * 2;     // program bytes of one sub-space for the workgroup: 16 x 48 uint16 = 1536
 constexpr uint32_t FC8_ROWBUF = 4u * FC8_SUBB;            // a stage's four sub-spaces: 6 KB
 
 struct FcOps8 {
@@ -994,12 +991,6 @@ hipError_t qk_conv_sym8(const ConvParams& p, hipStream_t st, int mode) {
     default: return hipErrorInvalidValue;
   }
 }
-
-bool qk_fc_sym8_shape(int D, int Ct, int M, int Cs, int K) {
-  return K == 32 && Cs == 4 && M % 4 == 0 && D == 4 * M && Ct >= 2 * FC8_CPW && Ct % 2 == 0;
-}
-int qk_fc_sym8_chunks(int Ct) { return (Ct + NW8 * FC8_CPW - 1) / (NW8 * FC8_CPW); }
-size_t qk_fc_sym8_program_bytes(int Ct, int M) { return (size_t)M * qk_fc_sym8_chunks(Ct) * FC8_SUBB; }
 
 hipError_t qk_build_program_fc8(const uint8_t* rows, uint16_t* prog, const QkSlots& src, int Ct, int M, hipStream_t st, int f16) {
   const size_t n = qk_fc_sym8_program_bytes(Ct, M) / sizeof(uint16_t);

@@ -1,5 +1,5 @@
 """The launch planner on the CPU (quantized-cnn_amd/csrc/qcnn_planner.{h,hip}: host code, built by g++ into
-build/libqcnn_planner_cpu.so — the same functions libqcnn_hip.so plans conv launches with).  Which kernel family runs
+build/libqcnn_planner_cpu.so — the same functions libqcnn_hip.so plans conv and FC launches with).  Which kernel family runs
 GetInPdMat + CalcFeatMap_ConvAprx (src/CaffeEva.cc:1261-1296, :760-868) for a launch geometry is a pure function of plain
 numbers; these tests pin the decisions the measured profiles are made of and the properties the decision rules promise."""
 import ctypes as C
@@ -145,3 +145,185 @@ def test_malformed_geometry_is_refused(planner):
     g = (C.c_int * 14)(13, 13, 256, 13, 13, 385, 3, 1, 1, 2, 32, 8, 128, 8)      # 385 channels in 2 groups
     o = (C.c_int * 8)(1, 1, 1, 1, 1, 1, 0, 64)
     assert lib.qcnn_plan_conv_query(g, o, None, None) != 0
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# FC layers: qk_choose_fc through qcnn_plan_fc_query.  The oracle below restates the rule as the engine's launch_layer spelt
+# it out before it moved into the planner (decoded slices, the two batch-independent picks, the per-launch re-pick under
+# QCNN_OPT_SPLIT, the clamp to what qk_fc_sym8 accepts, the scratch-fit fall-back to one pass).
+# ----------------------------------------------------------------------------------------------------------------------
+FC_WAVE12, FC_DEC, FC_SYM8, FC_SYM8_F16, FC_SYM8_F16SUM = -1, -3, -5, -7, -8
+AMPLE = -1
+MAX_FC_SPLIT = 32
+
+
+def _cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def fc_has_forms(D, Ct, M, K, Cs, P, flatten):
+    """(decoded form, eight-wave form) as qcnn_model_commit derives them from the layer's shape."""
+    s = _cdiv(Ct, 64) * 64
+    dec = (not flatten) and Cs == 1 and M == D and D % 64 == 0 and Ct >= 1 and D * 128 * 4 < 2 ** 32 and D * s * 4 < 2 ** 32
+    sym8 = P == 1 and K == 32 and Cs == 4 and M % 4 == 0 and D == 4 * M and Ct >= 192 and Ct % 2 == 0
+    return dec, sym8
+
+
+def fc_oracle(geom, split, sym8, decode, lut, small, flatten, scratch):
+    D, Ct, M, K, Cs, P, panels, live = geom
+    has_dec, has8 = fc_has_forms(D, Ct, M, K, Cs, P, flatten)
+    if decode and has_dec and lut == 1:
+        z = 1
+        if split:
+            wgs = _cdiv(Ct, 64) * panels * _cdiv(live, 64)
+            while wgs * z < 192 and D % (64 * 2 * z) == 0 and D // (64 * 2 * z) >= 4 and 2 * z <= 32:
+                z *= 2
+            z = min(z, MAX_FC_SPLIT)
+        if not (z > 1 and z * panels * Ct * 128 <= scratch):
+            z = 1
+        return FC_DEC, z
+    if P > 1:
+        return FC_WAVE12, 1
+    fc8h = bool(has8 and sym8 and lut >= 2 and not small)
+    fc8 = fc8h or bool(has8 and sym8 and lut == 1 and not small and (sym8 >= 2 or not split or panels >= 3))
+    msplit = 1
+    if lut >= 1:
+        G = 128 // K if K <= 64 else 1
+        stages = _cdiv(M, G)
+        cpb = 12 * (32 if Ct >= 384 else (8 if Ct >= 96 else 4))
+        chunks = _cdiv(Ct, 8 * 96) if fc8 else _cdiv(Ct, cpb)
+
+        def pick(min_stages):
+            best, best_fill = 1, 0.0
+            for cand in range(1, MAX_FC_SPLIT + 1):
+                if cand > 1 and stages // cand < min_stages:
+                    break
+                grid = chunks * cand * 8
+                fill = grid / (256.0 * _cdiv(grid, 256))
+                if fill > best_fill + 1e-9:
+                    best_fill, best = fill, cand
+            return best
+        ms = pick(24)
+        if chunks * ms < 64:
+            ms = pick(12)
+        if split and chunks * ms * panels < 2 * 256:
+            best, best_t = ms, 1e30
+            for cand in range(1, MAX_FC_SPLIT + 1):
+                if cand > 1 and stages // cand < 8:
+                    break
+                grid = chunks * cand * panels
+                t = float(_cdiv(grid, 256)) * (float(_cdiv(stages, cand)) + 10.0) + 0.5 * cand
+                if t < best_t - 1e-9:
+                    best_t, best = t, cand
+            ms = best
+        if ms > 1 and ms * panels * Ct * 128 <= scratch:
+            msplit = ms
+    if not fc8:
+        return FC_WAVE12, msplit
+    per = _cdiv(M // 4, msplit)
+    return (FC_SYM8_F16SUM if lut == 3 else FC_SYM8_F16) if fc8h else FC_SYM8, _cdiv(M // 4, per)
+
+
+@pytest.fixture(scope="module")
+def fc_planner():
+    lib = C.CDLL(build.build_planner_cpu())
+    lib.qcnn_plan_fc_query.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+
+    def query(geom, split=1, sym8=1, decode=1, lut=1, small=0, flatten=0, scratch=AMPLE):
+        ch = (C.c_int * 2)()
+        assert lib.qcnn_plan_fc_query((C.c_int * 8)(*geom), (C.c_int * 7)(split, sym8, decode, lut, small, flatten, scratch), ch) == 0
+        return ch[0], ch[1]
+    return query
+
+
+def fc_model_shapes(model):
+    """[(name, [D, Ct, M, K, Cs, P], flatten)] of a model's FC layers with the shipped quantisation shapes."""
+    in_chw, layers, _, _ = topo.MODELS[model]
+    sizes = topo.fmap_sizes(in_chw, layers)
+    spec = synth.quant_spec(in_chw, layers)
+    out = []
+    for i, l in enumerate(layers):
+        if l["type"] == topo.FCNT:
+            h, w, _ = sizes[i]
+            out.append(("%s/%d" % (model, i), [spec[i]["D"], spec[i]["Ct"], spec[i]["M"], spec[i]["K"], spec[i]["Cs"], 1], int(h * w > 1)))
+    return out
+
+
+def fc_shapes():
+    shapes = fc_model_shapes("AlexNet") + fc_model_shapes("VGG16")
+    for ct in (190, 192, 194, 384, 768, 1000, 4096):              # the eight-wave form needs Ct >= 192 and Ct even
+        for m4 in (1, 7, 8, 23, 24, 25, 96):
+            for k in (16, 32, 64, 128):
+                shapes.append(("seam", [16 * m4, ct, 4 * m4, k, 4, 1], 0))
+    for d in (64, 512, 4096):                                     # one-dim sub-spaces: the decoded form
+        shapes.append(("onedim", [d, 1000, d, 16, 1, 1], 0))
+    return shapes
+
+
+FC_PANELS, FC_LIVE = (1, 2, 3, 8, 32), (1, 64, 65, 128)
+FC_OPTIONS = [dict(split=s, sym8=y, lut=m, small=t) for s in (0, 1) for y in (0, 1, 2) for m in (0, 1, 2, 3) for t in (0, 1)]
+
+
+def fc_grid():
+    """(geom[8], options, flatten, scratch) over shapes x panels x live x options x {ample, one float short of the need}."""
+    for _, shape, flatten in fc_shapes():
+        for panels in FC_PANELS:
+            for live in FC_LIVE:
+                geom = shape + [panels, live]
+                for opt in FC_OPTIONS:
+                    _, z = fc_oracle(geom, decode=1, flatten=flatten, scratch=float("inf"), **opt)
+                    yield geom, opt, flatten, AMPLE
+                    yield geom, opt, flatten, z * panels * shape[1] * 128 - 1
+
+
+def test_fc_choice_matches_the_engine_rule(fc_planner):
+    n = 0
+    for geom, opt, flatten, scratch in fc_grid():
+        want = fc_oracle(geom, decode=1, flatten=flatten, scratch=float("inf") if scratch == AMPLE else scratch, **opt)
+        assert fc_planner(geom, flatten=flatten, scratch=scratch, **opt) == want, (geom, opt, flatten, scratch)
+        n += 1
+    assert n == len(fc_shapes()) * len(FC_PANELS) * len(FC_LIVE) * len(FC_OPTIONS) * 2
+    # QCNN_OPT_DECODE = 0 and pseudo sub-spaces (P > 1) take the table kernels' rule
+    for geom, opt in (([4096, 1000, 4096, 16, 1, 1, 1, 128], dict(decode=0)), ([4096, 1000, 2048, 128, 4, 2, 8, 128], {})):
+        assert fc_planner(geom, **opt) == fc_oracle(geom, **dict(dict(split=1, sym8=1, decode=1, lut=1, small=0, flatten=0, scratch=float("inf")), **opt))
+    assert fc_planner([4096, 1000, 2048, 128, 4, 2, 8, 128]) == (FC_WAVE12, 1)
+
+
+def test_fc_choice_properties(fc_planner):
+    by_key = {}
+    for geom, opt, flatten, scratch in fc_grid():
+        fam, z = fc_planner(geom, flatten=flatten, scratch=scratch, **opt)
+        D, Ct, M, K, Cs, P, panels, live = geom
+        ctx = (geom, opt, flatten, scratch)
+        assert 1 <= z <= MAX_FC_SPLIT, ctx
+        if fam in (FC_SYM8, FC_SYM8_F16, FC_SYM8_F16SUM):       # the condition qk_fc_sym8 enforces
+            stages = M // 4
+            assert _cdiv(stages, _cdiv(stages, z)) == z, ctx
+        # (a single pass writes no partial sums: the scratch only has to hold what a split launch writes)
+        assert z == 1 or scratch == AMPLE or z * panels * Ct * 128 <= scratch, ctx
+        if opt["lut"] == 0:
+            assert (fam, z) == (FC_WAVE12, 1), ctx
+        if opt["split"] == 0 and scratch == AMPLE:              # batch-size-invariant bits: the answer must not depend on the panels
+            key = (tuple(geom[:6]), live, flatten, tuple(sorted(opt.items())))
+            assert by_key.setdefault(key, (fam, z)) == (fam, z), ctx
+
+
+# (family, splits) of fc6, fc7, fc8 by panels: one or two panels stay with the 12-wave kernel (its split is not what
+# qcnn_get_layer_split reports), from three on fc6 / fc7 run eight-wave; fc8 (one-dim sub-spaces) runs decoded, in fewer k slices
+# the more panels fill the chip
+FC_PINS = {1: [(FC_WAVE12, 23), (FC_WAVE12, 20), (FC_DEC, 8)], 2: [(FC_WAVE12, 11), (FC_WAVE12, 11), (FC_DEC, 4)],
+           3: [(FC_SYM8, 14), (FC_SYM8, 14), (FC_DEC, 2)], 8: [(FC_SYM8, 16), (FC_SYM8, 16), (FC_DEC, 1)]}
+
+
+def test_fc_headline_decisions(fc_planner):
+    """AlexNet fc6 / fc7 / fc8 with library defaults at 1, 2, 3 and 8 panels of 128 images."""
+    (_, fc6, f6), (_, fc7, f7), (_, fc8, f8) = fc_model_shapes("AlexNet")
+    got = {p: [fc_planner(s + [p, 128], flatten=f) for s, f in ((fc6, f6), (fc7, f7), (fc8, f8))] for p in (1, 2, 3, 8)}
+    assert got == FC_PINS, got
+
+
+def test_fc_malformed_geometry_is_refused(fc_planner):
+    lib = C.CDLL(build.build_planner_cpu())
+    ch = (C.c_int * 2)()
+    assert lib.qcnn_plan_fc_query((C.c_int * 8)(4096, 1000, 1024, 0, 4, 1, 8, 128), (C.c_int * 7)(1, 1, 1, 1, 0, 0, -1), ch) != 0   # K = 0
+    assert lib.qcnn_plan_fc_query((C.c_int * 8)(4096, 1000, 1024, 32, 4, 1, 8, 129), (C.c_int * 7)(1, 1, 1, 1, 0, 0, -1), ch) != 0  # live > 128
