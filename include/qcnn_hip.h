@@ -323,7 +323,9 @@ int qcnn_run_layer(QcnnCtx* ctx, int layer, const float* in_host, int n, float* 
  * eight-wave symmetric workgroups (QCNN_OPT_SYM8): -5 (conv tile form, *slices = slices per tile under QCNN_OPT_SPLIT, else 1; FC:
  * *slices = splits of the sub-space axis), -6 in their sliding form (*slices = segments per output column;
  * qcnn_get_layer_segments reports the boundaries); their fp16-storage form (QCNN_OPT_LUT_MODE = 2): -7, with fp16 sums too
- * (QCNN_OPT_LUT_MODE = 3): -8. */
+ * (QCNN_OPT_LUT_MODE = 3): -8; the few-image kernels (QCNN_OPT_SMALL_BATCH, a forward of up to QCNN_SMALL_BATCH_MAX images, conv
+ * and FC layers): -11, *slices = 1 — only when they took the launch: a layer whose shape they do not cover (a tap window x K beyond
+ * their LDS table, an FC code book whose K is not a multiple of 4) reports the panel kernel that ran instead. */
 int qcnn_get_layer_split(QcnnCtx* ctx, int layer, int* tiles_unsplit, int* slices);
 /* Sliding kernel: the row segments [seg_beg9[i], seg_beg9[i + 1]) every output column of the last launch of `layer` was
  * cut into (*n_seg of them; 0 when the layer ran the tile kernel). */
@@ -336,7 +338,7 @@ int qcnn_get_layer_segments(QcnnCtx* ctx, int layer, int* seg_beg9, int* n_seg);
  *   QCNN_OPT_STREAMS > 1), partial-sum scratch in Mi floats.
  *   costs[7] (predicted stage-times; 0 = not eligible) = tile kernel, 16-wave sliding, 16-wave symmetric, eight-wave tile, eight-wave
  *   sliding, half-panel tile, half-panel sliding.     choice[13] = family code (what qcnn_get_layer_split reports: -1 tile, -2, -4, -5,
- *   -6, -9, -10), first split tile, slices, segments per column, nine segment boundaries.  Returns non-zero on a malformed geometry. */
+ *   -6, -9, -10; never -11: the few-image kernels are the engine's choice, not the planner's), first split tile, slices, segments per column, nine segment boundaries.  Returns non-zero on a malformed geometry. */
 int qcnn_plan_conv_query(const int* geom, const int* opts, double* costs, int* choice);
 
 /* ---- timing (QCNN_OPT_PROFILE = 1) ---- */

@@ -570,7 +570,10 @@ int launch_conv(QcnnCtx* c, int l, const Launch& L) {
   // table): the panel kernel handles every shape set_layer_shape accepts
   if (L.small) {
     const hipError_t e = qk_conv_small(p, L.live, st);
-    if (e != hipErrorInvalidValue) return launched(c, l, e);
+    if (e != hipErrorInvalidValue) {
+      s.lastFrom = -11; s.lastZ = 1;                  // reported by qcnn_get_layer_split as (-11, 1): the few-image kernel took the launch
+      return launched(c, l, e);
+    }
   }
   // fp16 table storage (QCNN_OPT_LUT_MODE = 2): the eight-wave tile kernel in its fp16 form wherever the layer's shape has one
   // (K = 128, complete 4- / 8-dim sub-spaces, > 64 channels per group); QCNN_OPT_SYM8 = 0 keeps every layer in the 16-wave
@@ -700,7 +703,10 @@ int launch_fc(QcnnCtx* c, int l, const Launch& L) {
   if (L.small && s.K % 4 == 0 && (size_t)L.live * s.M * s.K <= c->fcPartialElems) {
     p.partial = c->fcPartial;          // few images: the tables are materialised in the partial-sum scratch
     e = qk_fc_small(p, L.live, st);    // (K not a multiple of 4: the panel kernel below)
-    if (e != hipErrorInvalidValue) return launched(c, l, e);
+    if (e != hipErrorInvalidValue) {
+      s.lastFrom = -11; s.lastZ = 1;   // reported by qcnn_get_layer_split as (-11, 1): k_fc_lut + k_fc_small took the launch
+      return launched(c, l, e);
+    }
   }
   p.msplit = ch.splits; p.partial = partial;
   if (ch.family == QK_FC_WAVE12) {

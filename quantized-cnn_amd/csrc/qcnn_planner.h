@@ -43,6 +43,8 @@ struct QkConvPlan {
 // kernel family codes = what qcnn_get_layer_split reports as *tiles_unsplit for the conv table kernels
 enum QkConvFamily { QK_FAM_TILE = -1, QK_FAM_SLIDE16 = -2, QK_FAM_SYM16 = -4, QK_FAM_SYM8 = -5, QK_FAM_SYM8_SLIDE = -6,
                     QK_FAM_HALF8 = -9, QK_FAM_HALF8_SLIDE = -10 };
+// (-3: decoded code words, -7 / -8: fp16 tables / fp16 sums.  -11: the few-image kernels of qcnn_small.hip took the launch, conv or
+// FC — set by the engine, never chosen here; a few-image launch that falls through reports the panel family that then runs)
 struct QkConvChoice {
   int family;                             // QkConvFamily
   int splitFrom, Z;                       // QK_FAM_TILE: tiles from rank splitFrom on in Z slices (Z <= 1: whole); QK_FAM_SYM8: Z slices per tile

@@ -13,7 +13,11 @@
 // path interoperate; the assignment tables are the same one-byte row slots the panel kernels use (the code-word index
 // is recovered from the slot): one byte per look-up is streamed, as in the reference.  Summation runs over sub-space chunks first, so results agree
 // with the panel kernels / the reference to rounding (~1e-6), not bit for bit; the exact builder (QCNN_OPT_LUT_MODE = 0)
-// therefore always takes the panel kernels.
+// therefore always takes the panel kernels.  The table ENTRIES are the panel kernels' bit for bit: code books of 16 / 32 / 64 / 128
+// words are built on the matrix pipe (a k-ordered fused chain, like the panel kernels' MFMA builder), every other K by the
+// unfused sequence acc = acc + x_j * c_j of the exact builder, which is what the panel kernels run for such a K in every mode.
+// A stage holds G = qcnn_stage_group(K) sub-spaces — no power of two for K = 10, 20, 24, 40, ...: the position of sub-space m
+// inside its stage is m % G.
 #include "qcnn_kernels.h"
 
 #include <algorithm>
@@ -39,6 +43,7 @@ struct SmallConv {
   int srcNchw, img0;       // img0: index of image 0 of this launch inside the batch (NCHW addressing)
   int H, W, Cin, Ho, Wo, Ct, knl, stride, pad, grp;
   int M, Cs, K, G, relu, rowStride;
+  int mfma;                // K has an MFMA builder (16 / 32 / 64 / 128 code words); K = 128 then keeps its table in ROW-SLOT order
   int TH, TW, tilesX, CH, chunks, MC;   // output tile, channels per workgroup, chunks per group, sub-spaces per LUT chunk
   int lutFloats, xsFloats;              // LDS: table [npx][MC][K], activations [npx][MC * Cs], then assignments [taps][MC][CH] bytes
   QkSlots sl;
@@ -121,7 +126,7 @@ __global__ __launch_bounds__(NT) void k_conv_small(SmallConv p) {
     // ---- build: a thread owns a (sub-space, code word) pair, keeps the code word in registers and walks pixels; when
     //      there are fewer pairs than threads (first layer: one sub-space) the pixels are dealt out to NT / pairs thread
     //      groups.  Activation reads are LDS broadcasts, table writes are consecutive in k.
-    if (K % 16 == 0) {
+    if (p.mfma) {
       // Matrix build: the chunk's table is a small product [pixels x dims] x [dims x K] per sub-space — 16 x 16 tiles of
       // v_mfma_f32_16x16x4_f32 dealt out to the eight waves (A = staged activations out of LDS, B = the code book rows,
       // 64-byte segments from L2).  The scalar build below took a third of the kernel's time for one image.
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(NT) void k_conv_small(SmallConv p) {
           accT = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, accT, 0, 0, 0);
         }
         const int kc = ctile * 16 + li;
-        const int kst = (p.G == 1) ? qcnn_row_slot(kc) : kc;   // K = 128: entries in ROW-SLOT order, a look-up is tab[byte]
+        const int kst = (K == 128) ? qcnn_row_slot(kc) : kc;   // K = 128: entries in ROW-SLOT order, a look-up is tab[byte]
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int px = rt * 16 + 4 * kq + r;                  // D[4 kq + r][li]
@@ -148,12 +153,14 @@ __global__ __launch_bounds__(NT) void k_conv_small(SmallConv p) {
         }
       }
     } else {
+      // Any other K: the exact builder's sequence.  Entries in code-word order (the row-slot permutation stays inside groups of
+      // 16 rows, so a table of K entries holds it only where K is a multiple of 16: for K = 100 the slots of k = 97 .. 99 are
+      // 100, 104, 108, the next sub-space's first entries)
       const int npairs = mc * K;
       const int groups = npairs < NT ? NT / npairs : 1;
       const int pg = npairs < NT ? t / npairs : 0;
       for (int pair = (npairs < NT ? t % npairs : t); pair < npairs && pg < groups; pair += NT) {
         const int k = pair % K, mloc = pair / K;
-        const int kst = (p.G == 1) ? qcnn_row_slot(k) : k;   // K = 128: entries in ROW-SLOT order, a look-up is tab[byte]
         const int m = m0 + mloc;
         const int dsel = min(Cg - m * Cs, Cs);
         float cw[QCNN_MAX_CS];
@@ -164,8 +171,8 @@ __global__ __launch_bounds__(NT) void k_conv_small(SmallConv p) {
           float v = 0.0f;
 #pragma unroll
           for (int d = 0; d < QCNN_MAX_CS; ++d)
-            if (d < dsel) v = fmaf(xr[px * dims + d], cw[d], v);
-          lut[(px * p.MC + mloc) * K + kst] = v;
+            if (d < dsel) v = __fadd_rn(v, __fmul_rn(xr[px * dims + d], cw[d]));
+          lut[(px * p.MC + mloc) * K + k] = v;
         }
       }
     }
@@ -197,7 +204,7 @@ __global__ __launch_bounds__(NT) void k_conv_small(SmallConv p) {
 #pragma unroll
               for (int u = 0; u < 8; ++u) {
                 const float* tb = rowTab + (ptrdiff_t)min(kw + u, kwU) * (p.MC * K);
-                v[u] = (p.G == 1) ? tb[o[u]] : lut_at(tb, o[u], mi, K);
+                v[u] = (K == 128) ? tb[o[u]] : lut_at(tb, o[u], mi, K);
               }
 #pragma unroll
               for (int u = 0; u < 8; ++u)
@@ -215,7 +222,7 @@ __global__ __launch_bounds__(NT) void k_conv_small(SmallConv p) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                   const int mm = min(ml + u, mc - 1);
-                  v[u] = (p.G == 1) ? tab[mm * K + o[u]] : lut_at(tab + mm * K, o[u], (m0 + mm) & (p.G - 1), K);
+                  v[u] = (K == 128) ? tab[mm * K + o[u]] : lut_at(tab + mm * K, o[u], (m0 + mm) % p.G, K);
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
@@ -255,6 +262,7 @@ struct SmallFc {
   const uint8_t* cbn;      // or: the .cbn payload ([Ct][M] code words, `bits` each, 4096-byte blocks of `per` values), read in place
   int bits, per;
   int D, Ct, M, Cs, K, G, relu, rowStride, MC;
+  int mfma;                // K has an MFMA builder in the panel kernels: the entries are a fused chain; else the exact builder's sequence
   QkSlots sl;
 };
 
@@ -272,7 +280,10 @@ __global__ __launch_bounds__(256) void k_fc_lut(SmallFc p) {
   float v = 0.0f;
 #pragma unroll
   for (int d = 0; d < QCNN_MAX_CS; ++d)
-    if (d < dsel) v = fmaf(x[(size_t)(m * p.Cs + d) * PANEL], cm[d * p.K], v);
+    if (d < dsel) {
+      const float xv = x[(size_t)(m * p.Cs + d) * PANEL], cv = cm[d * p.K];
+      v = p.mfma ? fmaf(xv, cv, v) : __fadd_rn(v, __fmul_rn(xv, cv));
+    }
   p.lut[(size_t)img * p.M * p.K + e] = v;
 }
 
@@ -362,6 +373,9 @@ __global__ __launch_bounds__(NT) void k_fc_small(SmallFc p) {
   }
 }
 
+// the code-book sizes the panel kernels build on the matrix pipe (launch_conv / launch_fc in qcnn_kernels.hip)
+bool has_mfma_builder(int K) { return K == 16 || K == 32 || K == 64 || K == 128; }
+
 hipError_t allow_lds(const void* kern, int bytes) {
   return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
@@ -378,6 +392,7 @@ hipError_t qk_conv_small(const ConvParams& cp, int n, hipStream_t st) {
   p.H = cp.H; p.W = cp.W; p.Cin = cp.Cin; p.Ho = cp.Ho; p.Wo = cp.Wo; p.Ct = cp.Ct;
   p.knl = cp.knl; p.stride = cp.stride; p.pad = cp.pad; p.grp = cp.grp;
   p.M = cp.M; p.Cs = cp.Cs; p.K = cp.K; p.G = qcnn_stage_group(cp.K); p.relu = cp.relu;
+  p.mfma = has_mfma_builder(cp.K) ? 1 : 0;
   const int Ctg = cp.Ct / cp.grp;
   p.sl = qk_conv_slots(Ctg, cp.grp);
   p.rowStride = p.sl.rowStride;
@@ -417,6 +432,7 @@ hipError_t qk_fc_small(const FcParams& fp, int n, hipStream_t st) {
   p.cbn = (fp.cbnBits >= 1 && fp.cbnBits <= 8) ? fp.cbn : nullptr;
   p.bits = fp.cbnBits; p.per = p.cbn ? 4096 * 8 / fp.cbnBits : 1;
   p.D = fp.D; p.Ct = fp.Ct; p.M = fp.M; p.Cs = fp.Cs; p.K = fp.K; p.G = qcnn_stage_group(fp.K); p.relu = fp.relu;
+  p.mfma = has_mfma_builder(fp.K) ? 1 : 0;
   p.sl = qk_fc_slots(fp.Ct);
   p.rowStride = p.sl.rowStride;
   p.MC = std::min(fp.M, LUT_BYTES / (fp.K * 4));

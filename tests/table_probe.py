@@ -212,6 +212,81 @@ def check(y, want64, mag, n_terms, extra=0.0, relu=False, what=""):
     return float((err[~dead] / bound[~dead]).max()) if (~dead).any() else 0.0
 
 
+# ---------------------------------------------------------------- dense sums ----
+def dense_count(kind, g, M, Cs):
+    """Roundings behind one output element of a layer with ordinary parameters: an entry is a chain of CsEff fused multiply-adds
+    (or CsEff products and CsEff - 1 additions), the output a float32 sum of knl^2 M entries and the bias in any order, so
+    |y - want64| <= gamma(knl^2 M + CsEff + 1) * mag holds for every summation order, chunking and builder of the library."""
+    _, knl, _ = _dims(kind, g)
+    return knl * knl * M + max(cs_eff(kind, g, M, Cs)) + 1
+
+
+def dense_expected(kind, g, x, params):
+    """(want64, mag) of a layer with ordinary parameters (synth.make_params: bias, ctrd [M][K][Cs], asmt) on input x (layout of
+    `activations`), shaped like the layer's output [n, Ho, Wo, Ct] (FC: [n, Ct]), both float64:
+        want64 = bias + sum over the taps inside the map, over m, of <x_m, ctrd[m][asmt]>,   mag = |bias| + sum |x_j c_j|.
+    Plain numpy float64 throughout (every product of two float32 values is exact in float64)."""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    bias = np.asarray(params["bias"], np.float32).astype(np.float64)
+    ctrd = np.asarray(params["ctrd"], np.float32).astype(np.float64)
+    asmt = np.asarray(params["asmt"]).astype(np.int64)
+    M, K, Cs = ctrd.shape
+    cse = cs_eff(kind, g, M, Cs)
+    Ct = bias.shape[0]
+    if kind == "fc":
+        n = x.shape[0]
+        want = np.tile(bias, (n, 1))
+        mag = np.tile(np.abs(bias), (n, 1))
+        asmt = asmt.reshape(Ct, M)
+        for m in range(M):
+            xm, cm = x[:, m * Cs:m * Cs + cse[m]], ctrd[m, :, :cse[m]]
+            T, A = xm @ cm.T, np.abs(xm) @ np.abs(cm).T                          # [n, K]
+            want += T[:, asmt[:, m]]
+            mag += A[:, asmt[:, m]]
+        return want, mag
+    n, H, W, Cin = x.shape
+    knl, s, pad, grp = g["knl"], g["stride"], g["pad"], g["grp"]
+    Ho, Wo = out_hw(g)
+    Cg, Ctg = Cin // grp, Ct // grp
+    asmt = asmt.reshape(Ct, knl, knl, M)
+    want = np.tile(bias, (n, Ho, Wo, 1))
+    mag = np.tile(np.abs(bias), (n, Ho, Wo, 1))
+    for gi in range(grp):
+        cts = slice(gi * Ctg, (gi + 1) * Ctg)
+        for m in range(M):
+            c0 = gi * Cg + m * Cs
+            xm, cm = x[..., c0:c0 + cse[m]], ctrd[m, :, :cse[m]]
+            T, A = xm @ cm.T, np.abs(xm) @ np.abs(cm).T                          # [n, H, W, K]: the pixel tables of sub-space m
+            for kh in range(knl):
+                ho = [o for o in range(Ho) if 0 <= o * s - pad + kh < H]
+                for kw in range(knl):
+                    wo = [o for o in range(Wo) if 0 <= o * s - pad + kw < W]
+                    if not ho or not wo:
+                        continue
+                    hi = np.array(ho)[:, None] * s - pad + kh
+                    wi = np.array(wo)[None, :] * s - pad + kw
+                    a = asmt[cts, kh, kw, m]
+                    want[:, ho[0]:ho[-1] + 1, wo[0]:wo[-1] + 1, cts] += T[:, hi, wi][..., a]
+                    mag[:, ho[0]:ho[-1] + 1, wo[0]:wo[-1] + 1, cts] += A[:, hi, wi][..., a]
+    return want, mag
+
+
+def dense_check(y, want64, mag, n_terms, what=""):
+    """Assert |y - want64| <= gamma(n_terms) * mag for every element; returns the worst err / bound."""
+    y = np.asarray(y)
+    assert y.shape == want64.shape == mag.shape, (y.shape, want64.shape, mag.shape)
+    assert np.isfinite(y).all(), "%s: non-finite output" % what
+    assert (mag > 0).all()
+    err = np.abs(y.astype(np.float64) - want64)
+    ratio = err / (gamma(n_terms) * mag)
+    if (ratio > 1.0).any():
+        i = np.unravel_index(np.argmax(ratio), ratio.shape)
+        raise AssertionError("%s: %d of %d outputs beyond the bound; worst at %r: got %.9g want %.17g err %.3g bound %.3g"
+                             % (what, int((ratio > 1.0).sum()), ratio.size, i, float(y[i]), float(want64[i]), float(err[i]),
+                                float(gamma(n_terms) * mag[i])))
+    return float(ratio.max())
+
+
 def informative_share(mag):
     return float((mag > 0).mean())
 
@@ -272,7 +347,51 @@ SHAPES = {
     "fc6": ("fc", fc_geom(9216, 4096), 2304, 32, 4, 1),
     "fc200": ("fc", fc_geom(256, 200), 64, 32, 4, None),
     "fc_k16": ("fc", fc_geom(256, 1000), 256, 16, 1, None),
+    # the few-image kernels (qcnn_small.hip): the smallest shapes at which each sub-space chunk, stage group and tile edge of
+    # k_conv_small / k_fc_small is live.  SMALL_REACH states what each one reaches; tests/test_small_plan_cpu.py re-derives it from
+    # the launchers' tile / chunk rules
+    "sm_m18": ("conv", conv_geom(7, 7, 70, 3, 1, 1, 1, 64), 18, 128, 4, None),            # last sub-space: 2 of 4 dims
+    "sm_5x5_m12": ("conv", conv_geom(9, 9, 96, 5, 1, 2, 1, 128), 12, 128, 8, None),
+    "sm_k32_m24": ("conv", conv_geom(7, 7, 96, 5, 1, 2, 1, 128), 24, 32, 4, None),
+    "sm_k40": ("conv", conv_geom(7, 7, 16, 3, 1, 1, 1, 64), 4, 40, 4, None),
+    "sm_k24": ("conv", conv_geom(7, 7, 32, 3, 1, 1, 1, 64), 8, 24, 4, None),
+    "sm_k10_m6": ("conv", conv_geom(7, 7, 48, 3, 1, 1, 1, 64), 6, 10, 8, None),
+    "sm_k100_m6": ("conv", conv_geom(7, 7, 48, 3, 1, 1, 1, 64), 6, 100, 8, None),
+    "sm_ct400_g2": ("conv", conv_geom(7, 5, 24, 3, 2, 1, 2, 400), 3, 128, 4, None),
+    "sm_ct24": ("conv", conv_geom(5, 6, 16, 1, 2, 0, 1, 24), 2, 64, 8, None),
+    "sm_15_m2": ("conv", conv_geom(20, 20, 16, 15, 1, 0, 1, 16), 2, 128, 8, None),
+    "sm_15_k64": ("conv", conv_geom(20, 20, 16, 15, 1, 0, 1, 128), 2, 64, 8, None),
+    "sm_nchw_m2": ("conv", conv_geom(12, 12, 4, 3, 1, 1, 1, 16), 2, 128, 2, None),
+    # FC: thinned to the fewest rounds that name every m (ceil(M / Ct); the k shift of picks_of_round then names every k too):
+    # 23 of 698 rounds = 3.3 % of fc_m900's pairs, 8 of 147 = 5.5 % of fc_k128's, 57 of 844 = 6.8 % of fc_k16_m1800's
+    "fc_m900": ("fc", fc_geom(3600, 40), 900, 32, 4, 23),
+    "fc_k128": ("fc", fc_geom(920, 200), 230, 128, 4, 8),
+    "fc_k20": ("fc", fc_geom(240, 48), 60, 20, 4, None),
+    "fc_k16_m1800": ("fc", fc_geom(1800, 32), 1800, 16, 1, 57),
 }
+
+# What the few-image launchers must choose for each of those shapes (qk_conv_small: output tile, sub-spaces per table chunk,
+# channels per workgroup, channel chunks per group; qk_fc_small: sub-spaces per table chunk) for the case to reach the branch it
+# is there for: conv (TH, TW, MC, CH, channel chunks per group, G), FC (MC, G).
+SMALL_REACH = {
+    "sm_m18": (2, 2, 17, 64, 1, 1),           # sub-space chunks 17 + 1: m0 > 0, a ragged last chunk
+    "sm_5x5_m12": (2, 2, 7, 128, 1, 1),       # chunks 7 + 5; odd map: ragged 2x2 tiles
+    "sm_k32_m24": (2, 2, 19, 128, 1, 4),      # chunks 19 + 5: the second one starts mid-stage (19 mod 4 = 3)
+    "sm_k40": (2, 2, 4, 64, 1, 3),            # G = 3: no power of two; scalar build with fewer (m, k) pairs than threads
+    "sm_k24": (2, 2, 8, 64, 1, 5),            # G = 5
+    "sm_k10_m6": (2, 2, 6, 64, 1, 12),        # G = 12, m >= 4
+    "sm_k100_m6": (2, 2, 6, 64, 1, 1),        # scalar build with 600 >= 512 pairs, G = 1, K no multiple of 16
+    "sm_ct400_g2": (2, 2, 3, 128, 2, 1),      # 200 channels per group: two channel chunks, the second with 72 live lanes
+    "sm_ct24": (2, 2, 2, 32, 1, 2),           # 8 idle lanes, 16 position slots for 4 positions
+    "sm_15_m2": (1, 1, 1, 32, 1, 1),          # the mc == 1 gather at m0 = 1
+    "sm_15_k64": (1, 1, 1, 128, 1, 2),        # ... with mi = m0 % G = 1
+    "sm_nchw_m2": (2, 2, 2, 32, 1, 1),
+    "fc_m900": (896, 4), "fc_k128": (224, 1), "fc_k20": (60, 6), "fc_k16_m1800": (1792, 8),
+}
+
+# a 17x17 window with K = 128 on a 20x20 map: 289 pixels x (128 + 8) floats + 289 x 32 assignment bytes do not fit the few-image
+# kernel's LDS table at any tile, so a forward of one to three images hands this layer to the panel kernels
+SMALL_FALL_THROUGH = ("conv", conv_geom(20, 20, 8, 17, 1, 0, 1, 32), 1, 128, 8, None)
 
 
 def shape_rounds(name, negate=False):

@@ -178,8 +178,11 @@ def test_group_kernel_family_follows_the_global_batch(monkeypatch):
 
 
 def test_few_image_batches_fall_back_to_the_panel_kernels_where_needed():
-    """Shapes the few-image kernels do not cover — an FC code book whose K is not a multiple of 4, a conv window too
-    large for their LDS table (15x15 taps, K = 128) — run the panel kernels layer by layer instead of failing."""
+    """A shape the few-image kernels do not cover — an FC code book whose K is not a multiple of 4 (layer 2, K = 10) — runs the
+    panel kernel instead of failing, layer by layer: the 15x15 first layer with K = 128 still fits the few-image conv kernel's LDS
+    table (2x2 tile: 256 pixels x (128 + 8) floats + 225 x 32 assignment bytes = 146 464 B) and reports (-11, 1), layer 2 reports
+    the 12-wave panel kernel (-1, 1), the one-dim classifier (layer 4) its decoded form (QCNN_OPT_DECODE is on) or, where its
+    shape has none, the few-image FC kernel.  (A window that is too large — 17x17 — is tests/test_gpu_small_cases.py's.)"""
     in_chw = (3, 20, 20)
     layers = [topo.conv(0, 15, 16, 1, 1), topo.relu(), topo.fcnt(24), topo.relu(), topo.fcnt(10), topo.smax()]
     spec = synth.quant_spec(in_chw, layers, fc_k=10, fc_cs=4, last_k=16, last_cs=1)
@@ -191,6 +194,8 @@ def test_few_image_batches_fall_back_to_the_panel_kernels_where_needed():
         orc.forward(imgs)
         eng = _engine(in_chw, layers, params, 4, keep_all=1, small=1)
         prob, top5 = eng.forward_host(imgs)
+        codes = [eng.layer_split(l) for l in (0, 2, 4)]
+        assert codes[0] == (-11, 1) and codes[1] == (-1, 1) and codes[2][0] in (-3, -11), (n, codes)
         for l in range(len(layers) + 1):
             e_inf, e_l2 = rel_err(eng.layer_output(l, n), orc.fm(l))
             assert e_inf <= TOL and e_l2 <= TOL, "n=%d fm[%d]: %g %g" % (n, l, e_inf, e_l2)

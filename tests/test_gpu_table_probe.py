@@ -15,10 +15,14 @@ magnitude sum_j |x_j c_j| (nothing here is a max-norm over a map, and no bar is 
   * a tap in the padding gives exactly 0; an image's entries do not depend on its position in a panel or on the batch.
 
 Every case asserts the family code qcnn_get_layer_split reports (a silent fall-back to another family fails the case; the
-few-image kernels report the tile code (-1, 1): the library has no code of their own) and prints its worst err / bound.
+few-image kernels report (-11, 1) when they took the launch, and the panel kernel's code when the layer fell through to it)
+and prints its worst err / bound.
 Layer-for-layer cases go through qcnn_run_layer (any NHWC input, panel kernels, no ReLU); what only a forward reaches (the
 few-image kernels, the first layer read in place) goes through qcnn_forward_host, with the code book negated in a second
-pass where ReLU is fused.  fc6 (9216 -> 4096) runs ONE thinned round: 5.7 % of its 2304 x 31 (m, k) pairs, every m and every k."""
+pass where ReLU is fused.  fc6 (9216 -> 4096) runs ONE thinned round: 5.7 % of its 2304 x 31 (m, k) pairs, every m and every k.
+The sm_* / fc_m900 / fc_k128 / fc_k20 / fc_k16_m1800 shapes are the smallest at which each sub-space chunk, stage group and tile
+edge of the few-image kernels is live (table_probe.SMALL_REACH; tests/test_small_cases_cpu.py re-derives the launchers' choice);
+tests/test_gpu_small_cases.py runs the same shapes on dense sums."""
 import numpy as np
 import pytest
 
@@ -55,8 +59,8 @@ HALF8 = fam("half-panel tile", (-9, 1), n=(N_IMG, 5, 70), half8=2)
 HALF8S = fam("half-panel sliding", (-10, None), n=(N_IMG, 5, 70), half8=3)
 SPLIT_TILE = fam("split tiles, tile", ("split", None), n=(125,), split=1)
 SPLIT_SYM8 = fam("split tiles, eight-wave", (-5, "cut"), n=(125,), split=1, sym8=2)
-SMALL = fam("few-image", (-1, 1), via="forward", n=(1, 3), small=1)
-SMALL_PACKED = fam("few-image, packed FC", (-1, 1), via="forward", n=(1, 3), small=1, packed=1)
+SMALL = fam("few-image", (-11, 1), via="forward", n=(1, 3), small=1)
+SMALL_PACKED = fam("few-image, packed FC", (-11, 1), via="forward", n=(1, 3), small=1, packed=1)
 F16_CONV = [fam("fp16 tables", (-7, 1), like_tile=False, f16=True, lut=capi.LUT_MFMA_F16, sym8=2),
             fam("fp16 tables + sums", (-8, 1), like_tile=False, f16=True, lut=capi.LUT_MFMA_F16ACC, sym8=2)]
 F16_FC = [fam("fp16 tables", (-7, None), like_tile=False, f16=True, lut=capi.LUT_MFMA_F16, sym8=1),
@@ -86,10 +90,11 @@ CASES = [
     ("fc6", [TILE, FC_SYM8]),
     ("fc200", [EXACT, TILE, FC_SYM8]),
     ("fc_k16", [EXACT, TILE, DEC_FC]),
-]
+] + [(name, [EXACT, TILE, SMALL] + ([SMALL_PACKED] if tp.SHAPES[name][0] == "fc" else [])) for name in sorted(tp.SMALL_REACH)]
 
 FC_FRONT = {512: ((3, 3, 3), topo.conv(0, 3, 512, 1, 1)), 256: ((3, 3, 3), topo.conv(0, 3, 256, 1, 1)),
             9216: ((16, 6, 6), topo.conv(1, 3, 256, 1, 1))}      # a conv layer (no ReLU behind it) whose map has D elements
+FC_FRONT.update({d: ((3, 3, 3), topo.conv(0, 3, d, 1, 1)) for d in (3600, 920, 240, 1800)})
 
 
 def model_of(name):
