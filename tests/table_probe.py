@@ -368,6 +368,41 @@ SHAPES = {
     "fc_k128": ("fc", fc_geom(920, 200), 230, 128, 4, 8),
     "fc_k20": ("fc", fc_geom(240, 48), 60, 20, 4, None),
     "fc_k16_m1800": ("fc", fc_geom(1800, 32), 1800, 16, 1, 57),
+    # the decoded kernels (qcnn_decoded.hip): the smallest shapes at which each launch variant is live.  DEC_REACH states what
+    # each one reaches; tests/test_decoded_cases_cpu.py re-derives it from the launchers' rules.
+    # First layers read in place (pad 0, Ct % 96 == 0, one sub-space of Cin <= 4 dims)
+    "dn_k5": ("conv", conv_geom(9, 10, 3, 5, 1, 0, 1, 96), 1, 128, 4, None),
+    "dn_k5_k10": ("conv", conv_geom(9, 10, 3, 5, 1, 0, 1, 96), 1, 10, 4, None),           # a conv stage row is the code word itself,
+    "dn_k5_k100": ("conv", conv_geom(9, 10, 3, 5, 1, 0, 1, 96), 1, 100, 4, None),         # whatever K is
+    "dn_k4_s5": ("conv", conv_geom(9, 15, 1, 4, 5, 0, 1, 96), 1, 128, 4, None),
+    "dn_k6": ("conv", conv_geom(8, 22, 2, 6, 2, 0, 1, 96), 1, 128, 4, None),
+    "dn_k7_ct192": ("conv", conv_geom(9, 13, 3, 7, 2, 0, 1, 192), 1, 128, 4, None),
+    "dn_k9": ("conv", conv_geom(9, 9, 1, 9, 1, 0, 1, 96), 1, 128, 4, None),
+    "dn_flat_k9": ("conv", conv_geom(10, 11, 4, 9, 1, 0, 1, 96), 1, 128, 4, None),
+    "dn_f32_only": ("conv", conv_geom(8, 13, 4, 7, 3, 0, 1, 192), 1, 128, 4, None),
+    "dn_1x1": ("conv", conv_geom(2, 5, 1, 1, 1, 0, 1, 96), 1, 128, 4, None),
+    "dn_ct288": ("conv", conv_geom(6, 7, 3, 3, 1, 0, 1, 288), 1, 128, 4, None),
+    # panel form: 5 x 7 = 35 output positions, so that the position groups of 2, 4 and 6 all have a ragged tail
+    "dp_pad_k3": ("conv", conv_geom(5, 7, 3, 3, 1, 1, 1, 64), 1, 128, 4, None),
+    "dp_pad_c1": ("conv", conv_geom(5, 7, 1, 3, 1, 1, 1, 96), 1, 128, 4, None),
+    "dp_1x1": ("conv", conv_geom(5, 7, 3, 1, 1, 0, 1, 32), 1, 128, 4, None),
+    "dp_k7_ct32": ("conv", conv_geom(15, 19, 1, 7, 2, 0, 1, 32), 1, 128, 4, None),
+    "dp_k5_ct64": ("conv", conv_geom(9, 11, 2, 5, 1, 0, 1, 64), 1, 128, 4, None),
+    "dp_k2_ct96": ("conv", conv_geom(6, 8, 2, 2, 1, 0, 1, 96), 1, 128, 4, None),
+    "dp_k4_ct160": ("conv", conv_geom(8, 10, 1, 4, 1, 0, 1, 160), 1, 128, 4, None),
+    "dp_half_items": ("conv", conv_geom(48, 48, 2, 3, 1, 0, 1, 96), 1, 128, 4, None),     # (dense sums only, at 128 images)
+    # decoded FC (Cs = 1, M = D, D % 64 == 0), thinned to ceil(M / Ct) rounds — every m, and through the k shift every k: with the
+    # k = 0 rounds 15.3 % of fcd_d64's pairs, 20.0 % of fcd_d128_k10's, 8.6 / 2.4 % of fcd_d192_k24's / fcd_d320_k100's, 12.5 - 13.0 %
+    # of the four long ones'; fcd_d64_k128 (64 sub-spaces for 127 words) needs 43 of its 85 rounds to name every k: 51.6 %
+    "fcd_d64": ("fc", fc_geom(64, 40), 64, 16, 1, 2),
+    "fcd_d128_k10": ("fc", fc_geom(128, 64), 128, 10, 1, 2),
+    "fcd_d192_k24": ("fc", fc_geom(192, 66), 192, 24, 1, 3),             # (an odd channel count is refused at load: two live channels)
+    "fcd_d320_k100": ("fc", fc_geom(320, 130), 320, 100, 1, 3),
+    "fcd_d64_k128": ("fc", fc_geom(64, 96), 64, 128, 1, 43),
+    "fcd_d512": ("fc", fc_geom(512, 40), 512, 16, 1, 13),
+    "fcd_d640": ("fc", fc_geom(640, 40), 640, 16, 1, 16),
+    "fcd_d768": ("fc", fc_geom(768, 40), 768, 16, 1, 20),
+    "fcd_d2048": ("fc", fc_geom(2048, 40), 2048, 16, 1, 52),
 }
 
 # What the few-image launchers must choose for each of those shapes (qk_conv_small: output tile, sub-spaces per table chunk,
@@ -392,6 +427,115 @@ SMALL_REACH = {
 # a 17x17 window with K = 128 on a 20x20 map: 289 pixels x (128 + 8) floats + 289 x 32 assignment bytes do not fit the few-image
 # kernel's LDS table at any tile, so a forward of one to three images hands this layer to the panel kernels
 SMALL_FALL_THROUGH = ("conv", conv_geom(20, 20, 8, 17, 1, 0, 1, 32), 1, 128, 8, None)
+
+
+# What the decoded launchers must choose for each of those shapes for the case to reach the branch it is there for.
+#   dn_*: (in-place order under QCNN_OPT_DEC_BF16SPLIT: "runs" / "flat" / "f32" = no split form, runs per kernel row, padded k of the
+#          split kernel (0: none), padded k of the f32 in-place kernel, channel chunks, (Ho, Wo));
+#   dp_*: (S, NS, T = knl NS, instantiation <CT, PW, PADDED, R, IT> at more than 16 live images, the one at <= 16, channel chunks);
+#         T % R follows from them;
+#   fcd_*: (steps of four k per wave with one slice, G, 64-channel blocks, live channels of the last block, k slices under
+#          QCNN_OPT_SPLIT at one panel).
+DEC_REACH = {
+    "dn_k5": ("runs", 2, 128, 80, 1, (5, 6)),            # second run at column 1: three repeated columns; 30 runs in 32 slots
+    "dn_k5_k10": ("runs", 2, 128, 80, 1, (5, 6)),
+    "dn_k5_k100": ("runs", 2, 128, 80, 1, (5, 6)),
+    "dn_k4_s5": ("runs", 1, 32, 16, 1, (2, 3)),          # one run per row; ONE step, four of eight run slots live; column 14 unread
+    "dn_k6": ("runs", 2, 96, 80, 1, (2, 9)),             # overlap of two columns; 24 runs = exactly three steps
+    "dn_k7_ct192": ("runs", 2, 192, 160, 2, (2, 4)),     # overlap of one column; two channel chunks
+    "dn_k9": ("runs", 3, 128, 96, 1, (1, 1)),            # runs at columns 0, 4, 5
+    "dn_flat_k9": ("flat", 0, 352, 336, 1, (2, 3)),      # run order does not fit the LDS: Kr = 324 in Kb = 352
+    "dn_f32_only": ("f32", 0, 0, 208, 2, (1, 3)),        # neither split order fits: the f32 kernel under both option values
+    "dn_1x1": ("flat", 0, 32, 16, 1, (2, 5)),            # Kr = 1: 15 / 31 padded k
+    "dn_ct288": ("flat", 0, 32, 32, 3, (4, 5)),          # knl < 4: flat order; three channel chunks
+    "dp_pad_k3": (80, 3, 9, (4, 1, True, 2, 4), (2, 4, True, 2, 1), 1),
+    "dp_pad_c1": (112, 1, 3, (2, 1, True, 3, 4), (2, 4, True, 2, 1), 3),
+    "dp_1x1": (48, 1, 1, (2, 1, True, 3, 4), (2, 4, True, 2, 1), 1),
+    "dp_k7_ct32": (48, 2, 14, (2, 2, False, 3, 4), (2, 6, False, 3, 1), 1),
+    "dp_k5_ct64": (80, 3, 15, (4, 1, False, 3, 4), (4, 4, False, 3, 1), 1),
+    "dp_k2_ct96": (112, 1, 2, (6, 1, False, 2, 4), (6, 2, False, 3, 1), 1),
+    "dp_k4_ct160": (176, 1, 4, (2, 2, False, 3, 4), (2, 6, False, 3, 1), 5),
+    "dp_half_items": (112, 2, 6, (3, 1, False, 3, 4), (6, 2, False, 3, 1), 2),     # 4232 items at 128 images: half-items of 48 channels
+    "fcd_d64": (1, 8, 1, 40, 1), "fcd_d128_k10": (2, 12, 1, 64, 1), "fcd_d192_k24": (3, 5, 2, 2, 1),
+    "fcd_d320_k100": (5, 1, 3, 2, 1), "fcd_d64_k128": (1, 1, 2, 32, 1),
+    "fcd_d512": (8, 8, 1, 40, 2), "fcd_d640": (10, 8, 1, 40, 2), "fcd_d768": (12, 8, 1, 40, 2), "fcd_d2048": (32, 8, 1, 40, 8),
+}
+DEC_NCHW_SHAPES = sorted(n for n in DEC_REACH if n.startswith("dn_"))
+DEC_PANEL_SHAPES = sorted(n for n in DEC_REACH if n.startswith("dp_"))
+DEC_FC_SHAPES = sorted(n for n in DEC_REACH if n.startswith("fcd_"))
+DEC_BATCHES = (131, 70, 17, 16, 5)       # two panels with a ragged second one; two image halves; 17 and 16: either side of IT = 4 / 1
+DEC_NCHW_FEW = (3, 1)                    # one to three images still take the in-place kernel
+
+# Shapes that must NOT decode: more than 128 code words become pseudo sub-spaces, so the kernels see M = 2 for one sub-space
+# (conv) and M = 2 D (FC); the panel table kernel runs and reports its own code
+DEC_NOT = {
+    "nd_conv_k200": ("conv", conv_geom(9, 10, 3, 5, 1, 0, 1, 96), 1, 200, 4, None),
+    "nd_fc_k130": ("fc", fc_geom(64, 40), 64, 130, 1, None),
+}
+
+
+def dec_dense_rel(kind, g, split_bf16=False):
+    """Relative bound of one output of a decoded layer with ordinary parameters, per unit of mag = |bias| + sum |x_j c_j|, valid for
+    ANY summation order.  f32 (conv, both forms; FC with any slice count): the output is bias plus n = Cin knl^2 (FC: D) products
+    accumulated by fused multiply-adds — one rounding each, and partial chains joined by rounded additions never put more than n
+    roundings behind one term: gamma(n + 1).  Split-bf16: every product is six exact bf16 x bf16 terms that miss it by at most
+    2^-22 |x c| (test_bf16split_cpu.py), each added with one rounding: 2^-22 + gamma(6 n + 1)."""
+    n = g["Cin"] * g["knl"] ** 2 if kind == "conv" else g["D"]
+    return SPLIT_BF16_PRODUCT + gamma(6 * n + 1) if split_bf16 else gamma(n + 1)
+
+
+def dense_check_rel(y, want64, mag, rel, what=""):
+    """Assert |y - want64| <= rel * mag for every element; returns the worst err / bound."""
+    y = np.asarray(y)
+    assert y.shape == want64.shape == mag.shape, (y.shape, want64.shape, mag.shape)
+    assert np.isfinite(y).all(), "%s: non-finite output" % what
+    assert (mag > 0).all()
+    err = np.abs(y.astype(np.float64) - want64)
+    ratio = err / (rel * mag)
+    if (ratio > 1.0).any():
+        i = np.unravel_index(np.argmax(ratio), ratio.shape)
+        raise AssertionError("%s: %d of %d outputs beyond the bound; worst at %r: got %.9g want %.17g err %.3g bound %.3g"
+                             % (what, int((ratio > 1.0).sum()), ratio.size, i, float(y[i]), float(want64[i]), float(err[i]),
+                                float(rel * mag[i])))
+    return float(ratio.max())
+
+
+def dense_expected_one_subspace(g, x, params):
+    """dense_expected for a conv layer with ONE sub-space and one group, as knl^2 float64 matrix products over the decoded weights
+    (the same products, summed tap by tap): for maps too large for dense_expected's gathers.  tests/test_decoded_cases_cpu.py holds
+    it to dense_expected."""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    n, H, W, Cin = x.shape
+    knl, s, pad, Ct = g["knl"], g["stride"], g["pad"], g["Ct"]
+    assert g["grp"] == 1 and params["ctrd"].shape[0] == 1
+    Ho, Wo = out_hw(g)
+    a = np.asarray(params["asmt"]).reshape(Ct, knl, knl).astype(np.int64)
+    w = np.asarray(params["ctrd"], np.float32)[0][a][..., :Cin].astype(np.float64)      # [Ct, kh, kw, Cin]
+    xp = np.zeros((n, H + 2 * pad, W + 2 * pad, Cin))
+    xp[:, pad:pad + H, pad:pad + W] = x
+    bias = np.asarray(params["bias"], np.float32).astype(np.float64)
+    want = np.tile(bias, (n, Ho, Wo, 1))
+    mag = np.tile(np.abs(bias), (n, Ho, Wo, 1))
+    for kh in range(knl):
+        for kw in range(knl):
+            sl = xp[:, kh:kh + (Ho - 1) * s + 1:s, kw:kw + (Wo - 1) * s + 1:s]
+            want += sl @ w[:, kh, kw].T
+            mag += np.abs(sl) @ np.abs(w[:, kh, kw]).T
+    return want, mag
+
+
+def window_hit(g, poison):
+    """poison [n, H, W, Cin] bool -> [n, Ho, Wo] bool: the outputs whose window holds a poisoned input element."""
+    n, H, W, _ = poison.shape
+    knl, s, pad = g["knl"], g["stride"], g["pad"]
+    Ho, Wo = out_hw(g)
+    pp = np.zeros((n, H + 2 * pad, W + 2 * pad), bool)
+    pp[:, pad:pad + H, pad:pad + W] = poison.any(-1)
+    hit = np.zeros((n, Ho, Wo), bool)
+    for kh in range(knl):
+        for kw in range(knl):
+            hit |= pp[:, kh:kh + (Ho - 1) * s + 1:s, kw:kw + (Wo - 1) * s + 1:s]
+    return hit
 
 
 def shape_rounds(name, negate=False):

@@ -22,7 +22,13 @@ few-image kernels, the first layer read in place) goes through qcnn_forward_host
 pass where ReLU is fused.  fc6 (9216 -> 4096) runs ONE thinned round: 5.7 % of its 2304 x 31 (m, k) pairs, every m and every k.
 The sm_* / fc_m900 / fc_k128 / fc_k20 / fc_k16_m1800 shapes are the smallest at which each sub-space chunk, stage group and tile
 edge of the few-image kernels is live (table_probe.SMALL_REACH; tests/test_small_cases_cpu.py re-derives the launchers' choice);
-tests/test_gpu_small_cases.py runs the same shapes on dense sums."""
+tests/test_gpu_small_cases.py runs the same shapes on dense sums.
+The dn_* / dp_* / fcd_* shapes are the smallest at which each launch variant of the decoded kernels (qcnn_decoded.hip) is live
+(table_probe.DEC_REACH; tests/test_decoded_cases_cpu.py re-derives the launchers' choice): dn_* first layers read in place — the
+three k orders of the split-bf16 kernel, the f32 kernel, the shape only the f32 kernel takes —, dp_* the ten k_conv_dec
+instantiations (the 16-image ones only through a forward, whose launch knows how many images its panel holds), fcd_* k_fc_dec's
+ring tails, ragged channel block, stage groups and, under QCNN_OPT_SPLIT, its k slices; every decoded family runs them at 131,
+70, 17, 16 and 5 images (in place also at 3 and 1).  tests/test_gpu_decoded_cases.py runs the same shapes on dense sums."""
 import numpy as np
 import pytest
 
@@ -72,6 +78,37 @@ DEC_SPLIT = fam("decoded in place, split-bf16", (-3, 2), via="forward", like_til
                 keep_all=0, bf16split=1)
 DEC_FC = fam("decoded FC", (-3, 1), like_tile=False, decode=1)
 DECODED = [EXACT, TILE, DEC_PANEL, DEC_NCHW, DEC_SPLIT]
+# the decoded families at every batch size of table_probe.DEC_BATCHES.  A forward tells the launch how many images its one panel
+# holds (qcnn_run_layer always launches whole panels): only there do batches of <= 16 images reach the 16-image instantiations of
+# k_conv_dec and batches of <= 64 the one-half grid of k_fc_dec
+FWD_N = tuple(n for n in tp.DEC_BATCHES if n != N_IMG)
+DEC_PANEL_FWD = fam("decoded, panel form, forward", (-3, 1), via="forward", n=FWD_N, like_tile=False, decode=1)
+DEC_NCHW_N = dict(DEC_NCHW, n=tp.DEC_BATCHES)
+DEC_SPLIT_N = dict(DEC_SPLIT, n=tp.DEC_BATCHES)
+DEC_NCHW_FEW = fam("decoded in place, f32, few images", (-3, 2), via="forward", n=tp.DEC_NCHW_FEW, like_tile=False, relu=True, decode=1,
+                   keep_all=0, bf16split=0, small=1)
+DEC_SPLIT_FEW = fam("decoded in place, split-bf16, few images", (-3, 2), via="forward", n=tp.DEC_NCHW_FEW, like_tile=False, relu=True,
+                    split_bf16=True, decode=1, keep_all=0, bf16split=1, small=1)
+DEC_FC_FWD = fam("decoded FC, forward", (-3, 1), via="forward", n=FWD_N, like_tile=False, decode=1)
+DEC_FC_SLICES = fam("decoded FC, k slices", (-3, "cut"), like_tile=False, decode=1, split=1)
+DEC_FC_SLICES_FWD = fam("decoded FC, k slices, forward", (-3, "cut"), via="forward", n=FWD_N, like_tile=False, decode=1, split=1)
+
+
+def dec_families(name):
+    reach = tp.DEC_REACH[name]
+    if name.startswith("dp_"):
+        return [EXACT, TILE, DEC_PANEL, DEC_PANEL_FWD]
+    if name.startswith("fcd_"):
+        return [EXACT, TILE, DEC_FC, DEC_FC_FWD] + ([DEC_FC_SLICES, DEC_FC_SLICES_FWD] if reach[4] > 1 else [])
+    f32_only = dict(split_bf16=False) if reach[0] == "f32" else {}      # only the f32 kernel is eligible: its bound under both option values
+    fams = [EXACT, TILE, DEC_PANEL, DEC_PANEL_FWD, DEC_NCHW_N, dict(DEC_SPLIT_N, **f32_only)]
+    if tp.SHAPES[name][3] == 128:
+        return fams + [DEC_NCHW_FEW, dict(DEC_SPLIT_FEW, **f32_only)]
+    # another K: few images go to the few-image table kernel when it is on, and to the in-place kernel like every batch when it is off
+    return fams[:4] + [dict(f, n=tp.DEC_BATCHES + tp.DEC_NCHW_FEW) for f in fams[4:]]
+
+
+DEC_CASES = [n for n in tp.DEC_NCHW_SHAPES + tp.DEC_PANEL_SHAPES + tp.DEC_FC_SHAPES if n != "dp_half_items"]
 WIDE = [EXACT, TILE, SLIDE, SYM8, SYM8S, HALF8, HALF8S]
 
 CASES = [
@@ -90,11 +127,13 @@ CASES = [
     ("fc6", [TILE, FC_SYM8]),
     ("fc200", [EXACT, TILE, FC_SYM8]),
     ("fc_k16", [EXACT, TILE, DEC_FC]),
-] + [(name, [EXACT, TILE, SMALL] + ([SMALL_PACKED] if tp.SHAPES[name][0] == "fc" else [])) for name in sorted(tp.SMALL_REACH)]
+] + [(name, [EXACT, TILE, SMALL] + ([SMALL_PACKED] if tp.SHAPES[name][0] == "fc" else [])) for name in sorted(tp.SMALL_REACH)] + [
+    (name, dec_families(name)) for name in DEC_CASES]
 
 FC_FRONT = {512: ((3, 3, 3), topo.conv(0, 3, 512, 1, 1)), 256: ((3, 3, 3), topo.conv(0, 3, 256, 1, 1)),
             9216: ((16, 6, 6), topo.conv(1, 3, 256, 1, 1))}      # a conv layer (no ReLU behind it) whose map has D elements
 FC_FRONT.update({d: ((3, 3, 3), topo.conv(0, 3, d, 1, 1)) for d in (3600, 920, 240, 1800)})
+FC_FRONT.update({d: ((3, 3, 3), topo.conv(0, 3, d, 1, 1)) for d in (64, 128, 192, 320, 640, 768, 2048)})
 
 
 def model_of(name):
@@ -159,7 +198,7 @@ def test_table_probe(name, fams):
     p0 = tp.probe_params(kind, g, M, K, Cs, rounds[0], seed=31)
     engines = [make_engine(name, f["opts"], p0) for f in fams]
     c, h, w = model_of(name)[0]
-    images = tp.activations("conv", dict(H=h, W=w, Cin=c), 3, seed=33, scaled=False).transpose(0, 3, 1, 2)   # (forwards of FC cases)
+    images = tp.activations("conv", dict(H=h, W=w, Cin=c), N_IMG, seed=33, scaled=False).transpose(0, 3, 1, 2)   # (forwards of FC cases)
     labels = [f["label"] for f in fams]
     worst = {f["label"]: 0.0 for f in fams}
     share = 1.0
@@ -210,6 +249,8 @@ def test_table_probe(name, fams):
     for eng in engines:
         eng.close()
     assert share >= 0.5, share
+    if tp.SHAPES[name][5] is not None:
+        print("%s: %.1f %% of the (m, k) pairs" % (name, 100.0 * tp.covered(kind, g, M, K, rounds)[0].mean()))
     for f in fams:
         print("%s: %s code %r worst err / bound %.3f" % (name, f["label"], f["code"], worst[f["label"]]))
     assert all(v <= 1.0 for v in worst.values())
