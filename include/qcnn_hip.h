@@ -26,6 +26,8 @@
  *                               other), uploads overlapped with compute
  *   qcnn_host_register          pins CaffeEva::dataLst (LoadDataset)       src/CaffeEva.cc:95-107
  *   qcnn_forward_u8             BmpImgIO::RmMeanImg + CropImg in front     src/BmpImgIO.cc:180-224
+ *   qcnn_forward_u8_views       the same with any crop offsets and mirrors (CropImg takes the centre only), the views'
+ *   / qcnn_views_ten_crop       probabilities averaged on the device
  *   qcnn_model_set_layer_dense  CaffePara::LoadLayerPara(false, ..) result src/CaffePara.cc:290-302
  *   / _set_layer_weights        -> CalcFeatMap_ConvPrec / _FCntPrec        src/CaffeEva.cc:681-758, 932-966
  *   qcnn_quantize_layer         produces what CaffePara::LoadLayerPara reads src/CaffePara.cc:262-288
@@ -289,6 +291,34 @@ int qcnn_forward(QcnnCtx* ctx, const float* in_nchw_dev, int n, float* prob_dev,
  * a quarter of the host-to-device bytes. */
 int qcnn_forward_u8(QcnnCtx* ctx, const uint8_t* in_u8_dev, int src_h, int src_w, const float* mean_dev, int n,
                     float* prob_dev, uint16_t* top5_dev);
+/* Multi-view inference from the same 8-bit images: every image is evaluated on n_views crops of in_h x in_w pixels (the network
+ * input), each optionally mirrored left-right, and the class probabilities of its views are averaged — the ten-crop protocol
+ * the shipped networks are reported under, sliding-window and random-crop evaluation.  A view names the top-left corner of its
+ * crop inside the source image; flip != 0 mirrors the crop left-right. */
+#define QCNN_MAX_VIEWS 32
+typedef struct { int oy, ox, flip; } QcnnView;
+/* The standard ten views of a src_h x src_w image for an in_h x in_w network, in this order: the corners (0,0), (0,X), (Y,0),
+ * (Y,X) with Y = src_h - in_h, X = src_w - in_w, the centre ((src_h - in_h) / 2, (src_w - in_w) / 2) — the offsets
+ * qcnn_forward_u8 uses — then the same five with flip = 1.  Needs no device and no context.  Non-zero when the source is
+ * smaller than the input (or a size is not positive, or views10 is NULL). */
+int qcnn_views_ten_crop(int src_h, int src_w, int in_h, int in_w, QcnnView* views10);
+/* in_u8_dev / mean_dev as qcnn_forward_u8; views_host [n_views] in HOST memory, copied into the launch's arguments (nothing
+ * has to outlive the call).  Batch slot s = i * n_views + v holds view v of image i: element (c, y, x) of it is
+ * float(px[i][c][oy + y][xs]) - mean[c][oy + y][xs] with xs = ox + (flip ? in_w - 1 - x : x) — one convert, one subtract, the
+ * mean taken at the SOURCE position, so a mirrored view is the mirror of the plain one bit for bit and the centre view is
+ * qcnn_forward_u8's input.  The n * n_views <= max_batch slots run through the layers exactly as a batch of that size given
+ * to qcnn_forward_u8 would (same kernels, same bits; qcnn_get_layer_output afterwards addresses slots).
+ *   prob_views_dev [n][n_views][classes] or NULL   the rows of the slots, un-averaged
+ *   prob_dev [n][classes] or NULL                  fp32, one rounding per operation: s = p[view 0]; s = s + p[view v] for
+ *                                                  v = 1 .. n_views - 1 in that order; s / (float)n_views (n_views = 1: the row itself)
+ *   top5_dev [n][5] or NULL                        top-5 of the averaged rows, by the rule of every other entry point
+ * Every argument is checked before anything is launched: a model that is not committed, n <= 0, n_views outside
+ * [1, QCNN_MAX_VIEWS], n * n_views > max_batch and a view that leaves the source (oy < 0, ox < 0, oy + in_h > src_h,
+ * ox + in_w > src_w) return non-zero with nothing enqueued, and so does a source image of 2 GiB or more (offsets inside an
+ * image are 32-bit).  Asynchronous on the context's stream. */
+int qcnn_forward_u8_views(QcnnCtx* ctx, const uint8_t* in_u8_dev, int src_h, int src_w, const float* mean_dev, int n,
+                          const QcnnView* views_host, int n_views, float* prob_dev, uint16_t* top5_dev,
+                          float* prob_views_dev /* [n][n_views][classes] or NULL */);
 /* Blocking convenience: host in, host out (H2D + forward + D2H + sync).  A batch of at least two chunks
  * (QCNN_OPT_HOST_CHUNK) goes through chunk by chunk, uploads overlapped with the previous chunk's layers. */
 int qcnn_forward_host(QcnnCtx* ctx, const float* in_nchw_host, int n, float* prob_host, uint16_t* top5_host);

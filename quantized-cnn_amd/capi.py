@@ -24,6 +24,13 @@ class QcnnLayerDesc(C.Structure):
                 ("lrnAlp", C.c_float), ("lrnBet", C.c_float), ("lrnIni", C.c_float), ("drpRat", C.c_float)]
 
 
+MAX_VIEWS = 32             # QCNN_MAX_VIEWS (include/qcnn_hip.h)
+
+
+class QcnnView(C.Structure):
+    _fields_ = [("oy", C.c_int), ("ox", C.c_int), ("flip", C.c_int)]
+
+
 def layer_desc(ly: dict) -> QcnnLayerDesc:
     return QcnnLayerDesc(ly["type"], ly.get("pad", 0), ly.get("knl", 0), ly.get("cnt", 0), ly.get("grp", 0),
                          ly.get("stride", 0), ly.get("nod", 0), ly.get("siz", 0), ly.get("alp", 0.0),
@@ -72,6 +79,8 @@ def load():
     lib.qcnn_fm_dims.argtypes = [vp, i, C.POINTER(i)]
     lib.qcnn_forward.argtypes = [vp, f32p, i, f32p, u16p]
     lib.qcnn_forward_u8.argtypes = [vp, u8p, i, i, f32p, i, f32p, u16p]
+    lib.qcnn_views_ten_crop.argtypes = [i, i, i, i, C.POINTER(QcnnView)]
+    lib.qcnn_forward_u8_views.argtypes = [vp, u8p, i, i, f32p, i, C.POINTER(QcnnView), i, f32p, u16p, f32p]
     lib.qcnn_forward_host.argtypes = [vp, f32p, i, f32p, u16p]
     lib.qcnn_forward_host_batches.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp)]
     lib.qcnn_host_register.argtypes = [vp, C.c_size_t]

@@ -125,6 +125,8 @@ struct QcnnCtx {
   bool noConvPartial = false;        // ... could not be allocated: split plans launch their tiles whole
   size_t fcPartialElems = 0;
   size_t fcMaxCt = 0;
+  float* viewMean = nullptr;         // qcnn_forward_u8_views: panels [classes][128] of the probabilities averaged over an image's views —
+  size_t viewMeanElems = 0;          // allocated at its first call, grown when one needs more, freed with the context (no part of the plan)
   int lastN = 0;
   std::vector<float*> lastFm;        // pointer table of the last forward
 
@@ -945,6 +947,7 @@ int qcnn_ctx_destroy(QcnnCtx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   free_model(c);
+  if (c->viewMean) (void)hipFree(c->viewMean);
   for (int k = 0; k < kMaxStreams - 1; ++k) {
     if (c->aux[k]) (void)hipStreamDestroy(c->aux[k]);
     if (c->evJoin[k]) (void)hipEventDestroy(c->evJoin[k]);
@@ -1699,6 +1702,59 @@ int qcnn_forward_u8(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int src_w, 
   hipError_t e = qk_pack_u8(in_u8_dev, mean_dev, c->fmBuf[0], n, c->inC, c->inH, c->inW, src_h, src_w, c->stream);
   if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
   return forward_tail(c, n, prob_dev, top5_dev);
+}
+
+int qcnn_views_ten_crop(int src_h, int src_w, int in_h, int in_w, QcnnView* views10) {
+  if (!views10 || in_h <= 0 || in_w <= 0 || src_h < in_h || src_w < in_w) return 1;
+  const int Y = src_h - in_h, X = src_w - in_w;
+  const int five[5][2] = {{0, 0}, {0, X}, {Y, 0}, {Y, X}, {Y / 2, X / 2}};
+  for (int k = 0; k < 10; ++k) views10[k] = QcnnView{five[k % 5][0], five[k % 5][1], k / 5};
+  return 0;
+}
+
+static_assert(QK_MAX_VIEWS == QCNN_MAX_VIEWS, "the kernel-argument view table holds QCNN_MAX_VIEWS entries");
+
+int qcnn_forward_u8_views(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int src_w, const float* mean_dev, int n,
+                          const QcnnView* views_host, int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->committed) return fail(c, "model not committed");
+  if (!in_u8_dev || !views_host) return fail(c, "qcnn_forward_u8_views: images or views == NULL");
+  if (n <= 0) return fail(c, "batch %d: no image", n);
+  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
+  if ((long long)n * n_views > c->maxBatch)
+    return fail(c, "%d images x %d views = %lld batch slots, the model is committed for %d", n, n_views, (long long)n * n_views, c->maxBatch);
+  QkViews views = {};
+  for (int v = 0; v < n_views; ++v) {
+    const QcnnView& q = views_host[v];
+    if (q.oy < 0 || q.ox < 0 || q.oy > src_h - c->inH || q.ox > src_w - c->inW)
+      return fail(c, "view %d: the %dx%d crop at (%d, %d) leaves the %dx%d source image", v, c->inH, c->inW, q.oy, q.ox, src_h, src_w);
+    views.v[v] = QkView{q.oy, q.ox, q.flip ? 1 : 0};
+  }
+  const int slots = n * n_views, classes = (int)fm_elems(c, c->L);
+  const bool wantMean = prob_dev || top5_dev;
+  const size_t need = (size_t)((n + QCNN_PANEL - 1) / QCNN_PANEL) * classes * QCNN_PANEL;
+  if (wantMean && c->viewMeanElems < need) {          // grow: an earlier call on the stream may still be reading the old map
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->viewMean) (void)hipFree(c->viewMean);
+    c->viewMean = nullptr; c->viewMeanElems = 0;
+    HIP_TRY(c, hipMalloc(&c->viewMean, need * sizeof(float) + kSlack));
+    c->viewMeanElems = need;
+  }
+  hipError_t e = qk_pack_u8_views(in_u8_dev, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, src_h, src_w, c->stream);
+  if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
+  if (forward_tail(c, slots, prob_views_dev, nullptr)) return 1;     // the un-averaged rows: one per slot
+  if (!wantMean) return 0;
+  e = qk_mean_views(c->lastFm[c->L], c->viewMean, n, n_views, classes, c->stream);
+  if (e != hipSuccess) return fail(c, "view mean launch failed: %s", hipGetErrorString(e));
+  if (prob_dev) {
+    e = qk_unpack_rows(c->viewMean, prob_dev, n, classes, c->stream);
+    if (e != hipSuccess) return fail(c, "output unpack launch failed: %s", hipGetErrorString(e));
+  }
+  if (top5_dev) {
+    e = qk_top5(c->viewMean, top5_dev, n, classes, c->stream);
+    if (e != hipSuccess) return fail(c, "top-5 launch failed: %s", hipGetErrorString(e));
+  }
+  return 0;
 }
 
 int qcnn_host_register(void* ptr, size_t bytes) {

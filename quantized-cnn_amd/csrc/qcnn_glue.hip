@@ -1,12 +1,14 @@
 // qcnn_glue.hip — the glue kernels of the forward pass for gfx950: ReLU (src/CaffeEva.cc:1027),
 // LRN (:1038), max-pool (:870), the fused LRN + max-pool of the fast path, soft-max (:1098), top-5 (:1162), the sum of
 // the FC layers' split partial sums, and the conversions between the reference's NCHW / row-major host layouts and the
-// 128-image panels (:1146-1160, :187-189).  All of them are streaming kernels bound by HBM (or, for LRN, by the
+// 128-image panels (:1146-1160, :187-189), among them the 8-bit input pipelines (one centre crop per image, or several crops and
+// mirrors per image with the mean of their class probabilities: k_pack_u8_views, k_mean_views).  All of them are streaming kernels bound by HBM (or, for LRN, by the
 // expf/logf pair); the two hot kernels live in qcnn_kernels.hip.  Feature maps are panels [pixel][channel][128 images]
 // (qcnn_kernels.h); a float4 lane carries four images.
 #include "qcnn_kernels.h"
 
 #include <float.h>
+#include <limits.h>
 
 #include <algorithm>
 
@@ -560,6 +562,88 @@ __global__ __launch_bounds__(256) void k_pack_u8(const uint8_t* __restrict__ in,
   }
 }
 
+// Multi-view form of k_pack_u8 (qcnn_forward_u8_views): S = n * V batch slots, slot s = view s % V of image s / V — the H x W
+// crop at (oy, ox) of that view, mirrored left-right where it says so.  Same 128-slot x 64-element LDS transpose, same
+// arithmetic (float(pixel) - mean, the mean taken at the SOURCE position: a mirrored view is the mirror of the plain one bit
+// for bit), but source offset and mean now belong to the (slot, element) pair.  The element part of the offset (channel
+// plane + row, column and mirrored column) is the thread's own and computed once; the slot part (image, oy * Ws + ox, flip) is
+// the same for all lanes of a wave: it comes from the kernel arguments through scalar loads, and image / view advance by the
+// wave's slot stride of four without a division per slot.  The loads are UNCONDITIONAL — a dead slot reads image 0, a dead
+// element reads element 0 of the view, both inside the source; what is dead is zeroed on its way into the tile — because a
+// load under a per-lane condition is compiled into a branch with a full wait behind it, one round trip per load; like this the
+// eight pixel and eight mean loads of a round are in flight together.  MEAN = false: no mean image.  Pixels of the ten views of
+// an image overlap: a source image is read from HBM once and from L2 after that; the panels written are what bounds the kernel.
+template <bool MEAN>
+__global__ __launch_bounds__(256) void k_pack_u8_views(const uint8_t* __restrict__ in, const float* __restrict__ mean,
+                                                       float* __restrict__ dst, int S, int V, const QkViews views, int C, int H,
+                                                       int W, int Hs, int Ws) {
+  __shared__ float tile[PANEL][65];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int HW = H * W, E = C * HW;
+  const int e0 = blockIdx.x * 64;
+  const int panel = blockIdx.y;
+  const int e = e0 + lane;
+  const int el = e < E ? e : 0;                     // the element whose source position this thread reads
+  const unsigned rowOff = ((unsigned)(el / HW) * Hs + (el % HW) / W) * Ws;   // (c * Hs + y) * Ws: its row of the source at oy = 0
+  const unsigned off0 = rowOff + el % W, off1 = rowOff + (W - 1 - el % W);   // ... + its column in a plain / a mirrored view
+  const size_t srcImg = (size_t)C * Hs * Ws;        // < 2^31 (the launcher checks): offsets inside an image keep 32 bits
+  const int q4 = 4 / V, r4 = 4 % V;                 // the wave's next slot is four further: q4 images and r4 views
+  int img = (panel * PANEL + wave) / V, vw = (panel * PANEL + wave) % V;
+#pragma unroll
+  for (int b = 0; b < PANEL / 4; b += 8) {          // eight pixel (and eight mean) loads in flight per thread
+    uint8_t v[8];
+    float m[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const bool liveSlot = panel * PANEL + wave + 4 * (b + u) < S;     // wave-uniform
+      const QkView q = views.v[vw];                 // vw < V <= QK_MAX_VIEWS also for the dead slots of a ragged panel
+      const unsigned soff = (q.flip ? off1 : off0) + (unsigned)(q.oy * Ws + q.ox);
+      v[u] = (in + (size_t)(liveSlot ? img : 0) * srcImg)[soff];
+      m[u] = MEAN ? mean[soff] : 0.0f;
+      img += q4;
+      vw += r4;
+      if (vw >= V) { vw -= V; ++img; }
+    }
+    __builtin_amdgcn_sched_barrier(0);              // all sixteen loads are issued before the first value is waited for
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const bool live = panel * PANEL + wave + 4 * (b + u) < S && e < E;
+      tile[wave + 4 * (b + u)][lane] = live ? ((float)v[u] - m[u]) : 0.0f;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
+  for (int j = wave; j < 64; j += 4) {
+    const int ee = e0 + j;
+    if (ee < E) {
+      const int c = ee / HW, hw = ee % HW;
+      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)hw * C + c) * PANEL + 2 * lane) =
+          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
+    }
+  }
+}
+
+// Class probabilities of n * V slots -> their mean over the V views of each of n images, both in panels [C][128]: one thread =
+// one (image, class), s = p[view 0]; s = s + p[view v] in view order; s / (float)V, every operation rounded once (V = 1: the
+// row itself).  The slots of an image are neighbours but may lie on both sides of a panel seam; an image's lane of the output
+// panel is its own.  Dead lanes of a ragged output panel are zeros.  A few hundred KB: nothing here is worth tuning.
+__global__ __launch_bounds__(PANEL) void k_mean_views(const float* __restrict__ src, float* __restrict__ dst, int n, int V,
+                                                      int C) {
+  const int c = blockIdx.x, panel = blockIdx.y;
+  const int img = panel * PANEL + threadIdx.x;
+  float s = 0.0f;
+  if (img < n) {
+    size_t slot = (size_t)img * V;
+    s = src[((slot / PANEL) * C + c) * PANEL + slot % PANEL];
+    for (int v = 1; v < V; ++v) {
+      ++slot;
+      s = __fadd_rn(s, src[((slot / PANEL) * C + c) * PANEL + slot % PANEL]);
+    }
+    s = __fdiv_rn(s, (float)V);
+  }
+  dst[((size_t)panel * C + c) * PANEL + threadIdx.x] = s;
+}
+
 // panels [E][128] -> [n][E]
 __global__ __launch_bounds__(256) void k_unpack(const float* __restrict__ src, float* __restrict__ out, int n, int E) {
   __shared__ float tile[64][PANEL + 1];
@@ -714,6 +798,24 @@ hipError_t qk_pack_u8(const uint8_t* in, const float* mean, float* dst, int n, i
                       hipStream_t st) {
   const int E = C * H * W;
   hipLaunchKernelGGL(k_pack_u8, dim3((E + 63) / 64, panels_of(n)), dim3(256), 0, st, in, mean, dst, n, C, H, W, Hs, Ws);
+  return hipGetLastError();
+}
+
+hipError_t qk_pack_u8_views(const uint8_t* in, const float* mean, float* dst, int n, int V, const QkViews& views, int C, int H,
+                            int W, int Hs, int Ws, hipStream_t st) {
+  if (n <= 0 || V < 1 || V > QK_MAX_VIEWS) return hipErrorInvalidValue;
+  for (int v = 0; v < V; ++v)                       // a view outside the source must never reach the kernel
+    if (views.v[v].oy < 0 || views.v[v].ox < 0 || views.v[v].oy > Hs - H || views.v[v].ox > Ws - W) return hipErrorInvalidValue;
+  if ((long long)C * Hs * Ws > INT_MAX) return hipErrorInvalidValue;   // the kernel keeps offsets inside an image in 32 bits
+  const int E = C * H * W, S = n * V;
+  hipLaunchKernelGGL(mean ? k_pack_u8_views<true> : k_pack_u8_views<false>, dim3((E + 63) / 64, panels_of(S)), dim3(256), 0, st,
+                     in, mean, dst, S, V, views, C, H, W, Hs, Ws);
+  return hipGetLastError();
+}
+
+hipError_t qk_mean_views(const float* src, float* dst, int n, int V, int C, hipStream_t st) {
+  if (n <= 0 || V < 1 || C < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_mean_views, dim3(C, panels_of(n)), dim3(PANEL), 0, st, src, dst, n, V, C);
   return hipGetLastError();
 }
 

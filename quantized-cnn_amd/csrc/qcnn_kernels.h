@@ -426,6 +426,18 @@ hipError_t qk_pack_nchw(const float* in, float* dst, int n, int C, int H, int W,
 // 8-bit planar [n][C][Hs][Ws] minus mean [C][Hs][Ws] (or NULL), centre crop H x W -> panels [H*W*C][128]
 hipError_t qk_pack_u8(const uint8_t* in, const float* mean, float* dst, int n, int C, int H, int W, int Hs, int Ws,
                       hipStream_t st);
+// The views of qcnn_forward_u8_views, passed to the kernel BY VALUE (kernel arguments: no device table, nothing to outlive the
+// launch).  Same fields as QcnnView (include/qcnn_hip.h); the engine checked every view against the source size.
+#define QK_MAX_VIEWS 32
+struct QkView { int oy, ox, flip; };
+struct QkViews { QkView v[QK_MAX_VIEWS]; };
+// 8-bit planar [n][C][Hs][Ws] minus mean [C][Hs][Ws] (or NULL) -> panels [H*W*C][128] of n * V slots: slot i * V + v = the
+// H x W crop of image i at (views.v[v].oy, .ox), mirrored left-right where .flip (lanes >= n * V zero-filled)
+hipError_t qk_pack_u8_views(const uint8_t* in, const float* mean, float* dst, int n, int V, const QkViews& views, int C, int H,
+                            int W, int Hs, int Ws, hipStream_t st);
+// panels [C][128] of n * V slots -> panels [C][128] of n images: the mean over the V slots of an image, summed in slot order
+// in fp32 and divided by (float)V (lanes >= n zero-filled)
+hipError_t qk_mean_views(const float* src, float* dst, int n, int V, int C, hipStream_t st);
 // [n][E] (already in NHWC / flat order) -> panels [E][128]
 hipError_t qk_pack_rows(const float* in, float* dst, int n, int E, hipStream_t st);
 // panels [E][128] -> [n][E]

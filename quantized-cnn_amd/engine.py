@@ -237,6 +237,21 @@ class QcnnEngine:
                                            C.c_void_p(prob_ptr) if prob_ptr else None,
                                            C.c_void_p(top5_ptr) if top5_ptr else None))
 
+    def forward_u8_views_dev(self, in_ptr: int, src_h: int, src_w: int, mean_ptr: int | None, n: int, views,
+                             prob_ptr: int | None = None, top5_ptr: int | None = None, prob_views_ptr: int | None = None):
+        """Asynchronous, device pointers: multi-view inference from 8-bit planar images (qcnn_forward_u8_views).  views: a
+        sequence of (oy, ox, flip) — the top-left corner of a crop of the network's input size inside the source image,
+        flip: mirrored left-right (ten_crop_views gives the standard ten).  Batch slot i * len(views) + v is view v of image i;
+        prob [n][classes] / top5 [n][5] are those of the probabilities averaged over an image's views, prob_views
+        [n][len(views)][classes] the un-averaged rows."""
+        vs = [tuple(int(x) for x in v) for v in views]
+        arr = (capi.QcnnView * max(len(vs), 1))(*[capi.QcnnView(*v) for v in vs])
+        self._chk(self.lib.qcnn_forward_u8_views(self.h, C.c_void_p(in_ptr), src_h, src_w,
+                                                 C.c_void_p(mean_ptr) if mean_ptr else None, n, arr, len(vs),
+                                                 C.c_void_p(prob_ptr) if prob_ptr else None,
+                                                 C.c_void_p(top5_ptr) if top5_ptr else None,
+                                                 C.c_void_p(prob_views_ptr) if prob_views_ptr else None))
+
     def forward_host(self, imgs_nchw, want_prob=True, want_top5=True):
         imgs = np.ascontiguousarray(imgs_nchw, np.float32)
         n = imgs.shape[0]
@@ -317,6 +332,16 @@ def _host_batches(fn, obj, batches, out_hwc, want_prob, want_top5):
     a_t = (vp * nb)(*[t.ctypes.data for t in top5]) if want_top5 else None
     obj._chk(fn(obj.h, a_in, a_n, nb, a_p, a_t))
     return prob, top5
+
+
+def ten_crop_views(src_h: int, src_w: int, in_h: int, in_w: int):
+    """The standard ten views [(oy, ox, flip)] of a src_h x src_w image for an in_h x in_w network (qcnn_views_ten_crop): the
+    four corner crops and the centre crop, then their left-right mirrors.  Needs no device."""
+    lib = capi.load()
+    arr = (capi.QcnnView * 10)()
+    if lib.qcnn_views_ten_crop(src_h, src_w, in_h, in_w, arr):
+        raise QcnnError("ten_crop_views: a %dx%d source holds no %dx%d crop" % (src_h, src_w, in_h, in_w))
+    return [(v.oy, v.ox, v.flip) for v in arr]
 
 
 def host_register(arr) -> None:
