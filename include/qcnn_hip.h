@@ -28,6 +28,7 @@
  *   qcnn_forward_u8             BmpImgIO::RmMeanImg + CropImg in front     src/BmpImgIO.cc:180-224
  *   qcnn_forward_u8_views       the same with any crop offsets and mirrors (CropImg takes the centre only), the views'
  *   / qcnn_views_ten_crop       probabilities averaged on the device
+ *   qcnn_forward_u8_resized_views  BmpImgIO::ReszImg (Strict) in front of them, sources of any size  src/BmpImgIO.cc:105-178
  *   qcnn_model_set_layer_dense  CaffePara::LoadLayerPara(false, ..) result src/CaffePara.cc:290-302
  *   / _set_layer_weights        -> CalcFeatMap_ConvPrec / _FCntPrec        src/CaffeEva.cc:681-758, 932-966
  *   qcnn_quantize_layer         produces what CaffePara::LoadLayerPara reads src/CaffePara.cc:262-288
@@ -319,6 +320,35 @@ int qcnn_views_ten_crop(int src_h, int src_w, int in_h, int in_w, QcnnView* view
 int qcnn_forward_u8_views(QcnnCtx* ctx, const uint8_t* in_u8_dev, int src_h, int src_w, const float* mean_dev, int n,
                           const QcnnView* views_host, int n_views, float* prob_dev, uint16_t* top5_dev,
                           float* prob_views_dev /* [n][n_views][classes] or NULL */);
+/* The same from 8-bit source images of ANY size, each with its own: BmpImgIO::ReszImg (ENUM_ReszType::Strict,
+ * src/BmpImgIO.cc:105-178) on the device in front of RmMeanImg (ENUM_MeanType::Full) and the views, so that with the centre view
+ * alone the call is BmpImgIO::Load followed by the forward pass.  Image i is the planar [C][h][w] 8-bit image at src_dev +
+ * imgs_host[i].offset; it is resized to full_h x full_w in fp32 with one rounding per operation ((float) conversions of ints):
+ *   sh = (float)(h-1) / (float)(full_h-1)                          sw likewise
+ *   yc = sh * (float)y;  y0 = max(0, (int)yc);  y1 = min(h-1, y0+1)
+ *   wy0 = 1.0f - (yc - (float)y0);  wy1 = 1.0f - ((float)y1 - yc)  columns likewise -> x0, x1, wx0, wx1
+ *   w00 = wy0*wx0; w01 = wy0*wx1; w10 = wy1*wx0; w11 = wy1*wx1
+ *   num = ((p(y0,x0)*w00 + p(y0,x1)*w01) + p(y1,x0)*w10) + p(y1,x1)*w11        p = (float)pixel
+ *   out = num / (((w00 + w01) + w10) + w11)                                    IEEE division
+ * — the reference's bits (the division is not a no-op: at a clamped last row both row weights are about 1; a source of the full
+ * size comes out as its pixel values).  mean_dev [C][full_h][full_w] or NULL is subtracted at the full-image position, one fp32
+ * subtraction; the views are then cut from the full_h x full_w image and mirrored exactly as qcnn_forward_u8_views defines them
+ * on a source of that size.  The resized images are never stored: every element of a batch slot is computed from the four 8-bit
+ * taps of its image.  Slot order, the layers, the averaging, top-5 and the three outputs are those of qcnn_forward_u8_views.
+ * h == 1 or w == 1 is legal (the scale is 0 and both taps name the same pixel).
+ * imgs_host [n] and views_host [n_views] in HOST memory need not outlive the call: the descriptors are staged in pinned and
+ * device memory the context owns (grown on demand; a staging buffer is not rewritten before the call that reads it has passed).
+ * Every argument is checked before anything is enqueued — non-zero, a message in qcnn_last_error, outputs untouched: a model that
+ * is not committed, n <= 0, n_views outside [1, QCNN_MAX_VIEWS], n * n_views > max_batch, full_h < 2 or full_w < 2 (the scale
+ * divides by full - 1), a full image smaller than the network input (or of 2 GiB and more), a view that leaves the full image,
+ * h < 1 or w < 1, an image of 2 GiB or more (offsets inside an image are 32-bit), offset + C*h*w > src_bytes.  Asynchronous on
+ * the context's stream. */
+typedef struct { uint64_t offset; int32_t h, w; } QcnnSrcImage;   /* planar [C][h][w] 8-bit image at src_dev + offset */
+int qcnn_forward_u8_resized_views(QcnnCtx* ctx, const uint8_t* src_dev, size_t src_bytes,
+                                  const QcnnSrcImage* imgs_host, int n, int full_h, int full_w,
+                                  const float* mean_dev /* [C][full_h][full_w] or NULL */,
+                                  const QcnnView* views_host, int n_views,
+                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
 /* Blocking convenience: host in, host out (H2D + forward + D2H + sync).  A batch of at least two chunks
  * (QCNN_OPT_HOST_CHUNK) goes through chunk by chunk, uploads overlapped with the previous chunk's layers. */
 int qcnn_forward_host(QcnnCtx* ctx, const float* in_nchw_host, int n, float* prob_host, uint16_t* top5_host);

@@ -31,6 +31,11 @@ class QcnnView(C.Structure):
     _fields_ = [("oy", C.c_int), ("ox", C.c_int), ("flip", C.c_int)]
 
 
+class QcnnSrcImage(C.Structure):
+    """A source image of qcnn_forward_u8_resized_views: planar [C][h][w] 8-bit at `offset` bytes into the source buffer."""
+    _fields_ = [("offset", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 def layer_desc(ly: dict) -> QcnnLayerDesc:
     return QcnnLayerDesc(ly["type"], ly.get("pad", 0), ly.get("knl", 0), ly.get("cnt", 0), ly.get("grp", 0),
                          ly.get("stride", 0), ly.get("nod", 0), ly.get("siz", 0), ly.get("alp", 0.0),
@@ -81,6 +86,8 @@ def load():
     lib.qcnn_forward_u8.argtypes = [vp, u8p, i, i, f32p, i, f32p, u16p]
     lib.qcnn_views_ten_crop.argtypes = [i, i, i, i, C.POINTER(QcnnView)]
     lib.qcnn_forward_u8_views.argtypes = [vp, u8p, i, i, f32p, i, C.POINTER(QcnnView), i, f32p, u16p, f32p]
+    lib.qcnn_forward_u8_resized_views.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcImage), i, i, i, f32p, C.POINTER(QcnnView), i,
+                                                  f32p, u16p, f32p]
     lib.qcnn_forward_host.argtypes = [vp, f32p, i, f32p, u16p]
     lib.qcnn_forward_host_batches.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp)]
     lib.qcnn_host_register.argtypes = [vp, C.c_size_t]

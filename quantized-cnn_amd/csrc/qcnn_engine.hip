@@ -6,6 +6,7 @@
 // Everything the loop touches lives in HBM for the whole batch; the host only enqueues kernels.
 #include <hip/hip_runtime.h>
 
+#include <limits.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -127,6 +128,12 @@ struct QcnnCtx {
   size_t fcMaxCt = 0;
   float* viewMean = nullptr;         // qcnn_forward_u8_views: panels [classes][128] of the probabilities averaged over an image's views —
   size_t viewMeanElems = 0;          // allocated at its first call, grown when one needs more, freed with the context (no part of the plan)
+  // qcnn_forward_u8_resized_views: the source-image descriptors of a call travel host -> pinned -> device through one of two
+  // staging sets the context owns (first use, grown on demand, freed with the context).  ev is recorded behind the pack kernel
+  // that reads the set: the next call that takes the set waits for it before it rewrites (or frees) the buffers.
+  struct SrcStage { QkSrcImage* pin = nullptr; QkSrcImage* dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
+  SrcStage srcStage[2];
+  int srcStageNext = 0;
   int lastN = 0;
   std::vector<float*> lastFm;        // pointer table of the last forward
 
@@ -948,6 +955,11 @@ int qcnn_ctx_destroy(QcnnCtx* c) {
   (void)hipStreamSynchronize(c->stream);
   free_model(c);
   if (c->viewMean) (void)hipFree(c->viewMean);
+  for (QcnnCtx::SrcStage& g : c->srcStage) {
+    if (g.pin) (void)hipHostFree(g.pin);
+    if (g.dev) (void)hipFree(g.dev);
+    if (g.ev) (void)hipEventDestroy(g.ev);
+  }
   for (int k = 0; k < kMaxStreams - 1; ++k) {
     if (c->aux[k]) (void)hipStreamDestroy(c->aux[k]);
     if (c->evJoin[k]) (void)hipEventDestroy(c->evJoin[k]);
@@ -1714,6 +1726,38 @@ int qcnn_views_ten_crop(int src_h, int src_w, int in_h, int in_w, QcnnView* view
 
 static_assert(QK_MAX_VIEWS == QCNN_MAX_VIEWS, "the kernel-argument view table holds QCNN_MAX_VIEWS entries");
 
+namespace {
+// The multi-view calls around their pack kernel.  views_scratch (BEFORE the pack is launched): the map of the averaged rows is
+// large enough for n images.  views_tail: the layers on the n * n_views slots in fm[0], the un-averaged rows, the mean, top-5.
+int views_scratch(QcnnCtx* c, int n, bool wantMean) {
+  const size_t need = (size_t)((n + QCNN_PANEL - 1) / QCNN_PANEL) * fm_elems(c, c->L) * QCNN_PANEL;
+  if (wantMean && c->viewMeanElems < need) {          // grow: an earlier call on the stream may still be reading the old map
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->viewMean) (void)hipFree(c->viewMean);
+    c->viewMean = nullptr; c->viewMeanElems = 0;
+    HIP_TRY(c, hipMalloc(&c->viewMean, need * sizeof(float) + kSlack));
+    c->viewMeanElems = need;
+  }
+  return 0;
+}
+int views_tail(QcnnCtx* c, int n, int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  const int slots = n * n_views, classes = (int)fm_elems(c, c->L);
+  if (forward_tail(c, slots, prob_views_dev, nullptr)) return 1;     // the un-averaged rows: one per slot
+  if (!prob_dev && !top5_dev) return 0;
+  hipError_t e = qk_mean_views(c->lastFm[c->L], c->viewMean, n, n_views, classes, c->stream);
+  if (e != hipSuccess) return fail(c, "view mean launch failed: %s", hipGetErrorString(e));
+  if (prob_dev) {
+    e = qk_unpack_rows(c->viewMean, prob_dev, n, classes, c->stream);
+    if (e != hipSuccess) return fail(c, "output unpack launch failed: %s", hipGetErrorString(e));
+  }
+  if (top5_dev) {
+    e = qk_top5(c->viewMean, top5_dev, n, classes, c->stream);
+    if (e != hipSuccess) return fail(c, "top-5 launch failed: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+}  // namespace
+
 int qcnn_forward_u8_views(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int src_w, const float* mean_dev, int n,
                           const QcnnView* views_host, int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1730,31 +1774,69 @@ int qcnn_forward_u8_views(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int s
       return fail(c, "view %d: the %dx%d crop at (%d, %d) leaves the %dx%d source image", v, c->inH, c->inW, q.oy, q.ox, src_h, src_w);
     views.v[v] = QkView{q.oy, q.ox, q.flip ? 1 : 0};
   }
-  const int slots = n * n_views, classes = (int)fm_elems(c, c->L);
-  const bool wantMean = prob_dev || top5_dev;
-  const size_t need = (size_t)((n + QCNN_PANEL - 1) / QCNN_PANEL) * classes * QCNN_PANEL;
-  if (wantMean && c->viewMeanElems < need) {          // grow: an earlier call on the stream may still be reading the old map
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->viewMean) (void)hipFree(c->viewMean);
-    c->viewMean = nullptr; c->viewMeanElems = 0;
-    HIP_TRY(c, hipMalloc(&c->viewMean, need * sizeof(float) + kSlack));
-    c->viewMeanElems = need;
-  }
+  if (views_scratch(c, n, prob_dev || top5_dev)) return 1;
   hipError_t e = qk_pack_u8_views(in_u8_dev, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, src_h, src_w, c->stream);
   if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
-  if (forward_tail(c, slots, prob_views_dev, nullptr)) return 1;     // the un-averaged rows: one per slot
-  if (!wantMean) return 0;
-  e = qk_mean_views(c->lastFm[c->L], c->viewMean, n, n_views, classes, c->stream);
-  if (e != hipSuccess) return fail(c, "view mean launch failed: %s", hipGetErrorString(e));
-  if (prob_dev) {
-    e = qk_unpack_rows(c->viewMean, prob_dev, n, classes, c->stream);
-    if (e != hipSuccess) return fail(c, "output unpack launch failed: %s", hipGetErrorString(e));
+  return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_forward_u8_resized_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
+                                  int full_h, int full_w, const float* mean_dev, const QcnnView* views_host, int n_views,
+                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->committed) return fail(c, "model not committed");
+  if (!src_dev || !imgs_host || !views_host) return fail(c, "qcnn_forward_u8_resized_views: source buffer, images or views == NULL");
+  if (n <= 0) return fail(c, "batch %d: no image", n);
+  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
+  if ((long long)n * n_views > c->maxBatch)
+    return fail(c, "%d images x %d views = %lld batch slots, the model is committed for %d", n, n_views, (long long)n * n_views, c->maxBatch);
+  if (full_h < 2 || full_w < 2)
+    return fail(c, "full image %dx%d: the resize scale divides by full - 1, both sizes must be at least 2", full_h, full_w);
+  if (full_h < c->inH || full_w < c->inW)
+    return fail(c, "the full image %dx%d is smaller than the network input %dx%d", full_h, full_w, c->inH, c->inW);
+  if ((long long)c->inC * full_h * full_w > INT_MAX) return fail(c, "the full image %dx%dx%d has 2 GiB or more", c->inC, full_h, full_w);
+  QkViews views = {};
+  for (int v = 0; v < n_views; ++v) {
+    const QcnnView& q = views_host[v];
+    if (q.oy < 0 || q.ox < 0 || q.oy > full_h - c->inH || q.ox > full_w - c->inW)
+      return fail(c, "view %d: the %dx%d crop at (%d, %d) leaves the %dx%d full image", v, c->inH, c->inW, q.oy, q.ox, full_h, full_w);
+    views.v[v] = QkView{q.oy, q.ox, q.flip ? 1 : 0};
   }
-  if (top5_dev) {
-    e = qk_top5(c->viewMean, top5_dev, n, classes, c->stream);
-    if (e != hipSuccess) return fail(c, "top-5 launch failed: %s", hipGetErrorString(e));
+  for (int i = 0; i < n; ++i) {
+    const QcnnSrcImage& s = imgs_host[i];
+    if (s.h < 1 || s.w < 1) return fail(c, "image %d: size %dx%d", i, s.h, s.w);
+    const unsigned long long rows = (unsigned long long)c->inC * (unsigned long long)s.h, bytes = rows * (unsigned long long)s.w;   // rows <= INT_MAX is asked first: then bytes < 2^62
+    if (rows > (unsigned long long)INT_MAX || bytes > (unsigned long long)INT_MAX)
+      return fail(c, "image %d: %dx%dx%d has 2 GiB or more (offsets inside an image are 32-bit)", i, c->inC, s.h, s.w);
+    if (s.offset > src_bytes || bytes > src_bytes - s.offset)
+      return fail(c, "image %d: %llu bytes at offset %llu leave the source buffer of %zu bytes", i, bytes, (unsigned long long)s.offset, src_bytes);
   }
-  return 0;
+  // every argument is good: stage the descriptors.  The last reader of the set taken — the pack kernel of the call before the
+  // previous one — must have passed before its buffers are rewritten or freed.
+  QcnnCtx::SrcStage& g = c->srcStage[c->srcStageNext];
+  c->srcStageNext ^= 1;
+  if (!g.ev) HIP_TRY(c, hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
+  if (g.used) HIP_TRY(c, hipEventSynchronize(g.ev));
+  if (g.cap < (size_t)n) {
+    if (g.pin) (void)hipHostFree(g.pin);
+    if (g.dev) (void)hipFree(g.dev);
+    g.pin = nullptr; g.dev = nullptr; g.cap = 0; g.used = false;
+    const size_t cap = std::max<size_t>((size_t)n, 64);
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&g.pin), cap * sizeof(QkSrcImage), hipHostMallocPortable));
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&g.dev), cap * sizeof(QkSrcImage)));
+    g.cap = cap;
+  }
+  for (int i = 0; i < n; ++i) {                       // the scales: one IEEE division each, as ReszImg computes them
+    const QcnnSrcImage& s = imgs_host[i];
+    g.pin[i] = QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)};
+  }
+  if (views_scratch(c, n, prob_dev || top5_dev)) return 1;
+  g.used = true;                                      // from here on the set may be in flight
+  HIP_TRY(c, hipMemcpyAsync(g.dev, g.pin, (size_t)n * sizeof(QkSrcImage), hipMemcpyHostToDevice, c->stream));
+  hipError_t e = qk_pack_u8_resized(src_dev, g.dev, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
+  if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
+  HIP_TRY(c, hipEventRecord(g.ev, c->stream));
+  return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
 int qcnn_host_register(void* ptr, size_t bytes) {

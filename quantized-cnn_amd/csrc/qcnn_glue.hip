@@ -2,7 +2,8 @@
 // LRN (:1038), max-pool (:870), the fused LRN + max-pool of the fast path, soft-max (:1098), top-5 (:1162), the sum of
 // the FC layers' split partial sums, and the conversions between the reference's NCHW / row-major host layouts and the
 // 128-image panels (:1146-1160, :187-189), among them the 8-bit input pipelines (one centre crop per image, or several crops and
-// mirrors per image with the mean of their class probabilities: k_pack_u8_views, k_mean_views).  All of them are streaming kernels bound by HBM (or, for LRN, by the
+// mirrors per image with the mean of their class probabilities: k_pack_u8_views, k_mean_views; the same from source images of any
+// size, resized on the way: k_pack_u8_resized).  All of them are streaming kernels bound by HBM (or, for LRN, by the
 // expf/logf pair); the two hot kernels live in qcnn_kernels.hip.  Feature maps are panels [pixel][channel][128 images]
 // (qcnn_kernels.h); a float4 lane carries four images.
 #include "qcnn_kernels.h"
@@ -623,6 +624,87 @@ __global__ __launch_bounds__(256) void k_pack_u8_views(const uint8_t* __restrict
   }
 }
 
+// k_pack_u8_views on source images of any size (qcnn_forward_u8_resized_views): slot s = view s % V of image s / V RESIZED to
+// Hf x Wf, the reference's BmpImgIO::ReszImg (Strict, src/BmpImgIO.cc:105-178) fused into the pack — the resized float images
+// are never stored (a thousand 256 x 256 x 3 float images are 786 MB; the panels written are already the HBM bound).  Every
+// (slot, element) computes its value from the four 8-bit taps of the slot's image with the reference's fp32 sequence, one
+// rounding per operation (the build has -ffp-contract=off; the intrinsics say it again):
+//   yc = sh * (float)Y;  y0 = max(0, (int)yc);  y1 = min(h - 1, y0 + 1);  wy0 = 1 - (yc - (float)y0);  wy1 = 1 - ((float)y1 - yc)
+//   the columns likewise;  w00 = wy0 * wx0 ... w11 = wy1 * wx1
+//   (((p00 * w00 + p01 * w01) + p10 * w10) + p11 * w11) / (((w00 + w01) + w10) + w11) - mean[c][Y][X]
+// with (Y, X) the element's position in the full image: view corner + (y, x or the mirrored x).  yc is the float PRODUCT (for
+// some sizes it lands just under or over an integer it equals mathematically: that moves y0 and gives weights like 1 - eps or
+// above 1), and the division is no no-op (y1 clamped to y0 at the last row: both row weights about 1).  y0 is clamped to h - 1
+// as well: it cannot exceed it while h - 1 < 2^23, and beyond that the clamp keeps the taps inside the image.
+// Same 128-slot x 64-element LDS transpose as k_pack_u8_views and what it learned: the loads are unconditional (a dead slot
+// reads image 0 with image 0's own descriptor, a dead element reads element 0; dead values are zeroed on the way into the tile),
+// so the four tap loads and the mean load of all slots of a round are in flight together; the slot part of the addressing — the
+// image's descriptor from the table the engine staged, the view from the kernel arguments — is wave-uniform and comes through
+// scalar loads; offsets inside an image are 32-bit (the engine refuses images of 2 GiB and more).  The two scales of an image
+// come with its descriptor (QkSrcImage).  Eight slots a round: forty loads in flight per thread.
+template <bool MEAN>
+__global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restrict__ in, const QkSrcImage* __restrict__ desc,
+                                                         const float* __restrict__ mean, float* __restrict__ dst, int S, int V,
+                                                         const QkViews views, int C, int H, int W, int Hf, int Wf) {
+  __shared__ float tile[PANEL][65];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int HW = H * W, E = C * HW;
+  const int e0 = blockIdx.x * 64;
+  const int panel = blockIdx.y;
+  const int e = e0 + lane;
+  const int el = e < E ? e : 0;                     // the element whose source positions this thread reads
+  const int ch = el / HW, ey = (el % HW) / W;       // its channel and its row in a view
+  const int ex0 = el % W, ex1 = W - 1 - el % W;     // its column in a plain / a mirrored view
+  const int q4 = 4 / V, r4 = 4 % V;                 // the wave's next slot is four further: q4 images and r4 views
+  int img = (panel * PANEL + wave) / V, vw = (panel * PANEL + wave) % V;
+  constexpr int R = 8;                              // slots a round
+#pragma unroll
+  for (int b = 0; b < PANEL / 4; b += R) {
+    uint8_t p00[R], p01[R], p10[R], p11[R];
+    float w00[R], w01[R], w10[R], w11[R], m[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const bool liveSlot = panel * PANEL + wave + 4 * (b + u) < S;     // wave-uniform
+      const QkSrcImage d = desc[liveSlot ? img : 0];
+      const QkView q = views.v[vw];                 // vw < V <= QK_MAX_VIEWS also for the dead slots of a ragged panel
+      const int Y = q.oy + ey, X = q.ox + (q.flip ? ex1 : ex0);         // < Hf, < Wf: the engine checked the views
+      const float yc = __fmul_rn(d.sh, (float)Y), xc = __fmul_rn(d.sw, (float)X);
+      const int y0 = min(max(0, (int)yc), d.h - 1), x0 = min(max(0, (int)xc), d.w - 1);
+      const int y1 = min(d.h - 1, y0 + 1), x1 = min(d.w - 1, x0 + 1);
+      const float wy0 = __fsub_rn(1.0f, __fsub_rn(yc, (float)y0)), wy1 = __fsub_rn(1.0f, __fsub_rn((float)y1, yc));
+      const float wx0 = __fsub_rn(1.0f, __fsub_rn(xc, (float)x0)), wx1 = __fsub_rn(1.0f, __fsub_rn((float)x1, xc));
+      w00[u] = __fmul_rn(wy0, wx0); w01[u] = __fmul_rn(wy0, wx1); w10[u] = __fmul_rn(wy1, wx0); w11[u] = __fmul_rn(wy1, wx1);
+      const uint8_t* px = in + d.off;
+      const unsigned r0 = ((unsigned)ch * d.h + y0) * d.w, r1 = ((unsigned)ch * d.h + y1) * d.w;   // < C * h * w <= INT_MAX
+      p00[u] = px[r0 + x0]; p01[u] = px[r0 + x1]; p10[u] = px[r1 + x0]; p11[u] = px[r1 + x1];
+      m[u] = MEAN ? mean[((unsigned)ch * Hf + Y) * Wf + X] : 0.0f;
+      img += q4;
+      vw += r4;
+      if (vw >= V) { vw -= V; ++img; }
+    }
+    __builtin_amdgcn_sched_barrier(0);              // every load of the round is issued before the first value is waited for
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const bool live = panel * PANEL + wave + 4 * (b + u) < S && e < E;
+      const float num = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn((float)p00[u], w00[u]), __fmul_rn((float)p01[u], w01[u])),
+                                            __fmul_rn((float)p10[u], w10[u])), __fmul_rn((float)p11[u], w11[u]));
+      const float den = __fadd_rn(__fadd_rn(__fadd_rn(w00[u], w01[u]), w10[u]), w11[u]);
+      const float val = __fdiv_rn(num, den);
+      tile[wave + 4 * (b + u)][lane] = live ? (MEAN ? __fsub_rn(val, m[u]) : val) : 0.0f;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
+  for (int j = wave; j < 64; j += 4) {
+    const int ee = e0 + j;
+    if (ee < E) {
+      const int c = ee / HW, hw = ee % HW;
+      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)hw * C + c) * PANEL + 2 * lane) =
+          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
+    }
+  }
+}
+
 // Class probabilities of n * V slots -> their mean over the V views of each of n images, both in panels [C][128]: one thread =
 // one (image, class), s = p[view 0]; s = s + p[view v] in view order; s / (float)V, every operation rounded once (V = 1: the
 // row itself).  The slots of an image are neighbours but may lie on both sides of a panel seam; an image's lane of the output
@@ -810,6 +892,18 @@ hipError_t qk_pack_u8_views(const uint8_t* in, const float* mean, float* dst, in
   const int E = C * H * W, S = n * V;
   hipLaunchKernelGGL(mean ? k_pack_u8_views<true> : k_pack_u8_views<false>, dim3((E + 63) / 64, panels_of(S)), dim3(256), 0, st,
                      in, mean, dst, S, V, views, C, H, W, Hs, Ws);
+  return hipGetLastError();
+}
+
+hipError_t qk_pack_u8_resized(const uint8_t* in, const QkSrcImage* desc, const float* mean, float* dst, int n, int V,
+                              const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st) {
+  if (n <= 0 || V < 1 || V > QK_MAX_VIEWS || !in || !desc || Hf < 2 || Wf < 2) return hipErrorInvalidValue;
+  for (int v = 0; v < V; ++v)                       // a view outside the full image must never reach the kernel
+    if (views.v[v].oy < 0 || views.v[v].ox < 0 || views.v[v].oy > Hf - H || views.v[v].ox > Wf - W) return hipErrorInvalidValue;
+  if ((long long)C * Hf * Wf > INT_MAX) return hipErrorInvalidValue;   // the mean's offsets are 32-bit too
+  const int E = C * H * W, S = n * V;
+  hipLaunchKernelGGL(mean ? k_pack_u8_resized<true> : k_pack_u8_resized<false>, dim3((E + 63) / 64, panels_of(S)), dim3(256), 0,
+                     st, in, desc, mean, dst, S, V, views, C, H, W, Hf, Wf);
   return hipGetLastError();
 }
 

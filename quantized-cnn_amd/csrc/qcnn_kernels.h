@@ -435,6 +435,16 @@ struct QkViews { QkView v[QK_MAX_VIEWS]; };
 // H x W crop of image i at (views.v[v].oy, .ox), mirrored left-right where .flip (lanes >= n * V zero-filled)
 hipError_t qk_pack_u8_views(const uint8_t* in, const float* mean, float* dst, int n, int V, const QkViews& views, int C, int H,
                             int W, int Hs, int Ws, hipStream_t st);
+// A source image of qcnn_forward_u8_resized_views as the kernel reads it from the descriptor table the engine stages: the
+// QcnnSrcImage (include/qcnn_hip.h) and its two scales sh = (float)(h - 1) / (float)(Hf - 1), sw likewise — one IEEE division
+// each, done once per image on the host instead of once per (slot, element) on the device.
+struct QkSrcImage { unsigned long long off; int h, w; float sh, sw; };
+// 8-bit planar images [C][h_i][w_i] at in + desc[i].off, each resized to Hf x Wf (BmpImgIO::ReszImg, Strict) minus mean
+// [C][Hf][Wf] (or NULL) -> panels [H*W*C][128] of n * V slots: slot i * V + v = the H x W crop of resized image i at
+// (views.v[v].oy, .ox), mirrored left-right where .flip (lanes >= n * V zero-filled).  desc [n] in DEVICE memory; the caller
+// checked every descriptor against the source buffer (h, w >= 1, C * h * w <= INT_MAX, inside the buffer).
+hipError_t qk_pack_u8_resized(const uint8_t* in, const QkSrcImage* desc, const float* mean, float* dst, int n, int V,
+                              const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st);
 // panels [C][128] of n * V slots -> panels [C][128] of n images: the mean over the V slots of an image, summed in slot order
 // in fp32 and divided by (float)V (lanes >= n zero-filled)
 hipError_t qk_mean_views(const float* src, float* dst, int n, int V, int C, hipStream_t st);

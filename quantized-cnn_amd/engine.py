@@ -252,6 +252,56 @@ class QcnnEngine:
                                                  C.c_void_p(top5_ptr) if top5_ptr else None,
                                                  C.c_void_p(prob_views_ptr) if prob_views_ptr else None))
 
+    def forward_u8_resized_views_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int, mean_ptr: int | None,
+                                     views, prob_ptr: int | None = None, top5_ptr: int | None = None,
+                                     prob_views_ptr: int | None = None):
+        """Asynchronous, device pointers: multi-view inference from 8-bit planar images of ANY size, each resized to
+        full_h x full_w on the device (qcnn_forward_u8_resized_views: BmpImgIO::ReszImg, Strict, in front of the mean and the
+        views).  descs: a sequence of (offset, h, w) — image i is [C][h][w] at src_ptr + offset (pack_sources makes buffer and
+        list); mean [C][full_h][full_w] or None; views as forward_u8_views_dev takes them, cut from the full image.  Neither
+        list has to outlive the call."""
+        if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcImage:     # made once by the caller: no per-call conversion
+            darr, n = descs, len(descs)
+        else:
+            ds = [tuple(int(x) for x in d) for d in descs]
+            darr, n = (capi.QcnnSrcImage * max(len(ds), 1))(*[capi.QcnnSrcImage(*d) for d in ds]), len(ds)
+        vs = [tuple(int(x) for x in v) for v in views]
+        varr = (capi.QcnnView * max(len(vs), 1))(*[capi.QcnnView(*v) for v in vs])
+        self._chk(self.lib.qcnn_forward_u8_resized_views(self.h, C.c_void_p(src_ptr), src_bytes, darr, n, full_h, full_w,
+                                                         C.c_void_p(mean_ptr) if mean_ptr else None, varr, len(vs),
+                                                         C.c_void_p(prob_ptr) if prob_ptr else None,
+                                                         C.c_void_p(top5_ptr) if top5_ptr else None,
+                                                         C.c_void_p(prob_views_ptr) if prob_views_ptr else None))
+
+    def forward_u8_resized_host(self, images, full_hw, mean=None, views=None):
+        """Blocking convenience: images — a list of uint8 arrays [C][h][w] of differing sizes — are packed, uploaded, resized
+        to full_hw = (full_h, full_w) on the device, the float32 mean [C][full_h][full_w] (or None) subtracted, and evaluated on
+        `views` (default: the centre crop alone, which makes the call BmpImgIO::Load + the forward pass).  Returns (prob
+        [n][classes] averaged over the views, top5 [n][5], prob_views [n][len(views)][classes]) as numpy arrays."""
+        import torch   # plumbing only: device buffers and copies
+        full_h, full_w = int(full_hw[0]), int(full_hw[1])
+        _, in_h, in_w = self.in_chw
+        if views is None:
+            views = [((full_h - in_h) // 2, (full_w - in_w) // 2, 0)]
+        flat, descs = pack_sources(images)
+        n, V = len(descs), len(views)
+        fh, fw, fc = self.fm_dims(self.L)
+        classes = fh * fw * fc
+        dev = torch.device("cuda", self.lib.qcnn_ctx_device(self.h))
+        d_src = torch.from_numpy(flat).to(dev)
+        d_mean = torch.from_numpy(np.ascontiguousarray(mean, np.float32)).to(dev) if mean is not None else None
+        if d_mean is not None and tuple(d_mean.shape) != (self.in_chw[0], full_h, full_w):
+            raise QcnnError("mean image %r, expected %r" % (tuple(d_mean.shape), (self.in_chw[0], full_h, full_w)))
+        d_prob = torch.empty((n, classes), dtype=torch.float32, device=dev)
+        d_top5 = torch.empty((n, 5), dtype=torch.int16, device=dev)
+        d_rows = torch.empty((n, max(V, 1), classes), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.forward_u8_resized_views_dev(d_src.data_ptr(), flat.size, descs, full_h, full_w,
+                                          d_mean.data_ptr() if d_mean is not None else None, views,
+                                          d_prob.data_ptr(), d_top5.data_ptr(), d_rows.data_ptr())
+        self.sync()
+        return d_prob.cpu().numpy(), d_top5.cpu().numpy().view(np.uint16), d_rows.cpu().numpy()
+
     def forward_host(self, imgs_nchw, want_prob=True, want_top5=True):
         imgs = np.ascontiguousarray(imgs_nchw, np.float32)
         n = imgs.shape[0]
@@ -342,6 +392,27 @@ def ten_crop_views(src_h: int, src_w: int, in_h: int, in_w: int):
     if lib.qcnn_views_ten_crop(src_h, src_w, in_h, in_w, arr):
         raise QcnnError("ten_crop_views: a %dx%d source holds no %dx%d crop" % (src_h, src_w, in_h, in_w))
     return [(v.oy, v.ox, v.flip) for v in arr]
+
+
+def pack_sources(images):
+    """A list of uint8 arrays [C][h][w] of differing sizes (one channel count) -> (flat uint8 buffer with the images back to
+    back in order, [(offset, h, w)]): what qcnn_forward_u8_resized_views reads once the buffer is on the device.  Needs no
+    device."""
+    imgs = list(images)
+    if not imgs:
+        raise ValueError("pack_sources: no image")
+    descs, off = [], 0
+    for k, a in enumerate(imgs):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.size == 0:
+            raise ValueError("pack_sources: image %d is not a uint8 array [C][h][w]" % k)
+        if a.shape[0] != imgs[0].shape[0]:
+            raise ValueError("pack_sources: image %d has %d channels, image 0 has %d" % (k, a.shape[0], imgs[0].shape[0]))
+        descs.append((off, int(a.shape[1]), int(a.shape[2])))
+        off += a.size
+    flat = np.empty(off, np.uint8)
+    for a, (o, _, _) in zip(imgs, descs):
+        flat[o:o + a.size] = a.reshape(-1)
+    return flat, descs
 
 
 def host_register(arr) -> None:
