@@ -29,6 +29,7 @@
  *   qcnn_forward_u8_views       the same with any crop offsets and mirrors (CropImg takes the centre only), the views'
  *   / qcnn_views_ten_crop       probabilities averaged on the device
  *   qcnn_forward_u8_resized_views  BmpImgIO::ReszImg (Strict) in front of them, sources of any size  src/BmpImgIO.cc:105-178
+ *   qcnn_forward_u8_relaxed_views  ReszImg (Relaxed) + CropImg + a crop-sized mean (VggCnnS) in front  src/BmpImgIO.cc:56-64,124-131
  *   qcnn_model_set_layer_dense  CaffePara::LoadLayerPara(false, ..) result src/CaffePara.cc:290-302
  *   / _set_layer_weights        -> CalcFeatMap_ConvPrec / _FCntPrec        src/CaffeEva.cc:681-758, 932-966
  *   qcnn_quantize_layer         produces what CaffePara::LoadLayerPara reads src/CaffePara.cc:262-288
@@ -348,6 +349,48 @@ int qcnn_forward_u8_resized_views(QcnnCtx* ctx, const uint8_t* src_dev, size_t s
                                   const QcnnSrcImage* imgs_host, int n, int full_h, int full_w,
                                   const float* mean_dev /* [C][full_h][full_w] or NULL */,
                                   const QcnnView* views_host, int n_views,
+                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
+/* The reference's OTHER pre-processing mode, ENUM_ReszType::Relaxed + ENUM_MeanType::Crop (VggCnnS, src/CaffeEvaWrapper.cc:69-76;
+ * src/BmpImgIO.cc:56-64,124-131), on the device: the image is resized by ONE scale for both axes — the aspect ratio is kept, the
+ * full size differs per image — then cropped, then a mean of the CROP's size is subtracted.  For a source of h x w pixels and the
+ * nominal full size full_h x full_w, in fp32 with one rounding per operation ((float) conversions of ints):
+ *   sh = (float)(h-1) / (float)(full_h-1);   sw = (float)(w-1) / (float)(full_w-1)
+ *   s  = min(sh, sw)                                        lines 127-128 leave BOTH scales equal to s
+ *   Hf = (int)((double)((float)(h-1) / s) + 1e-7) + 1       int / float is a float division, kEpsilon a double, the cast truncates
+ *   Wf = (int)((double)((float)(w-1) / s) + 1e-7) + 1
+ * and the image is resampled to Hf x Wf by the sequence of qcnn_forward_u8_resized_views with s as both scales: yc = s * (float)Y,
+ * the taps, the four weight products, the left-to-right sums, the IEEE division.  The float quotient is NOT the mathematical
+ * one: the side that sets the scale may come out one pixel under the nominal size (37 x 53 at 256 x 256 gives 255 x 369, 2 x 2
+ * gives 255 x 255; 30 x 8 at 12 x 14 gives 54 x 13), so "the smaller side becomes full" does not hold for the reference's bits
+ * and every view is checked against every image's own Hf x Wf.
+ * qcnn_relaxed_full_size is that size rule: host only, needs no device and no context; scale may be NULL.  Non-zero (nothing
+ * written) for h < 2 or w < 2 (s would be 0 and the reference casts inf / NaN to int: refused, not reproduced), full_h < 2 or
+ * full_w < 2, an Hf or Wf of 2^24 or more ((float)Y would not be exact), hf or wf == NULL. */
+int qcnn_relaxed_full_size(int h, int w, int full_h, int full_w, int* hf, int* wf, float* scale);
+/* a view placed relative to each image's OWN full size: a = 0 near edge, 1 = CropImg's centre (full - in) / 2, 2 = far edge (full - in);
+ * d = pixels added to it */
+typedef struct { int ay, ax, dy, dx, flip; } QcnnAnchorView;
+/* The standard ten views as anchors, in the order of qcnn_views_ten_crop: the corners (0,0), (0,2), (2,0), (2,2), the centre
+ * (1,1), all with d = 0, then the same five with flip = 1 — for an image whose full size is Hf x Wf they resolve to
+ * qcnn_views_ten_crop(Hf, Wf, in_h, in_w).  Needs no device and no context.  Non-zero when views10 is NULL. */
+int qcnn_views_ten_crop_anchored(QcnnAnchorView* views10);
+/* Multi-view inference in that mode.  src_dev, src_bytes, imgs_host as qcnn_forward_u8_resized_views takes them.  View v of image
+ * i has its corner at oy = a(ay) + dy, ox = a(ax) + dx with a(0) = 0, a(1) = (F - in) / 2 (integer division: CropImg's corner),
+ * a(2) = F - in and F that image's Hf resp. Wf.  Element (c, y, x) of batch slot i * n_views + v is
+ *   R_i[c][oy + y][ox + xl] - mean_crop[c][y][xl],   xl = flip ? in_w - 1 - x : x
+ * with R_i the resampled image (never stored: every element is computed from the four 8-bit taps) and mean_crop_dev
+ * [C][in_h][in_w] or NULL: one fp32 subtraction, the mean taken at the view-local position BEFORE mirroring (the reference has no
+ * mirrors; the rule is the invariant of qcnn_forward_u8_views), so a mirrored view is the mirror of the plain one bit for bit and
+ * the centre anchor alone is BmpImgIO::Load of a Relaxed / Crop model followed by the forward pass.  Slot order, the layers, the
+ * averaging, top-5, the three optional outputs and the staging of imgs_host / views_host (neither has to outlive the call) are
+ * those of qcnn_forward_u8_resized_views.
+ * Every argument is checked before anything is enqueued — non-zero, a message in qcnn_last_error, outputs untouched: everything
+ * qcnn_forward_u8_resized_views checks (with h < 2 or w < 2 in place of h < 1 or w < 1), an Hf or Wf of 2^24 or more, ay or ax
+ * outside 0..2, and for every image SEPARATELY a resolved view that leaves that image's Hf x Wf: one such image refuses the whole
+ * call, the message names the image and the view.  Asynchronous on the context's stream. */
+int qcnn_forward_u8_relaxed_views(QcnnCtx* ctx, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
+                                  int full_h, int full_w, const float* mean_crop_dev /* [C][in_h][in_w] or NULL */,
+                                  const QcnnAnchorView* views_host, int n_views,
                                   float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
 /* Blocking convenience: host in, host out (H2D + forward + D2H + sync).  A batch of at least two chunks
  * (QCNN_OPT_HOST_CHUNK) goes through chunk by chunk, uploads overlapped with the previous chunk's layers. */

@@ -36,6 +36,12 @@ class QcnnSrcImage(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class QcnnAnchorView(C.Structure):
+    """A view of qcnn_forward_u8_relaxed_views, placed relative to each image's own full size: anchor 0 / 1 / 2 = near edge /
+    CropImg's centre / far edge on each axis, plus dy / dx pixels; flip: mirrored left-right."""
+    _fields_ = [("ay", C.c_int), ("ax", C.c_int), ("dy", C.c_int), ("dx", C.c_int), ("flip", C.c_int)]
+
+
 def layer_desc(ly: dict) -> QcnnLayerDesc:
     return QcnnLayerDesc(ly["type"], ly.get("pad", 0), ly.get("knl", 0), ly.get("cnt", 0), ly.get("grp", 0),
                          ly.get("stride", 0), ly.get("nod", 0), ly.get("siz", 0), ly.get("alp", 0.0),
@@ -87,6 +93,10 @@ def load():
     lib.qcnn_views_ten_crop.argtypes = [i, i, i, i, C.POINTER(QcnnView)]
     lib.qcnn_forward_u8_views.argtypes = [vp, u8p, i, i, f32p, i, C.POINTER(QcnnView), i, f32p, u16p, f32p]
     lib.qcnn_forward_u8_resized_views.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcImage), i, i, i, f32p, C.POINTER(QcnnView), i,
+                                                  f32p, u16p, f32p]
+    lib.qcnn_views_ten_crop_anchored.argtypes = [C.POINTER(QcnnAnchorView)]
+    lib.qcnn_relaxed_full_size.argtypes = [i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_float)]
+    lib.qcnn_forward_u8_relaxed_views.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcImage), i, i, i, f32p, C.POINTER(QcnnAnchorView), i,
                                                   f32p, u16p, f32p]
     lib.qcnn_forward_host.argtypes = [vp, f32p, i, f32p, u16p]
     lib.qcnn_forward_host_batches.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp)]

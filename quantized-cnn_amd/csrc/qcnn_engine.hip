@@ -131,7 +131,8 @@ struct QcnnCtx {
   // qcnn_forward_u8_resized_views: the source-image descriptors of a call travel host -> pinned -> device through one of two
   // staging sets the context owns (first use, grown on demand, freed with the context).  ev is recorded behind the pack kernel
   // that reads the set: the next call that takes the set waits for it before it rewrites (or frees) the buffers.
-  struct SrcStage { QkSrcImage* pin = nullptr; QkSrcImage* dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
+  // qcnn_forward_u8_relaxed_views stages its QkRelaxedImage table through the same two sets: cap counts bytes.
+  struct SrcStage { void* pin = nullptr; void* dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
   SrcStage srcStage[2];
   int srcStageNext = 0;
   int lastN = 0;
@@ -1740,6 +1741,27 @@ int views_scratch(QcnnCtx* c, int n, bool wantMean) {
   }
   return 0;
 }
+// The next of the two descriptor staging sets, large enough for n descriptors of `each` bytes (at least 64 of them); nullptr
+// after fail().  The last reader of the set taken — the pack kernel of the call before the previous one — must have passed
+// before its buffers are rewritten or freed.
+QcnnCtx::SrcStage* stage_take(QcnnCtx* c, size_t n, size_t each) {
+  QcnnCtx::SrcStage& g = c->srcStage[c->srcStageNext];
+  c->srcStageNext ^= 1;
+  hipError_t e = hipSuccess;
+  if (!g.ev) e = hipEventCreateWithFlags(&g.ev, hipEventDisableTiming);
+  if (e == hipSuccess && g.used) e = hipEventSynchronize(g.ev);
+  if (e == hipSuccess && g.cap < n * each) {
+    if (g.pin) (void)hipHostFree(g.pin);
+    if (g.dev) (void)hipFree(g.dev);
+    g.pin = nullptr; g.dev = nullptr; g.cap = 0; g.used = false;
+    const size_t cap = std::max<size_t>(n, 64) * each;
+    e = hipHostMalloc(&g.pin, cap, hipHostMallocPortable);
+    if (e == hipSuccess) e = hipMalloc(&g.dev, cap);
+    if (e == hipSuccess) g.cap = cap;
+  }
+  if (e != hipSuccess) { fail(c, "descriptor staging: %s", hipGetErrorString(e)); return nullptr; }
+  return &g;
+}
 int views_tail(QcnnCtx* c, int n, int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
   const int slots = n * n_views, classes = (int)fm_elems(c, c->L);
   if (forward_tail(c, slots, prob_views_dev, nullptr)) return 1;     // the un-averaged rows: one per slot
@@ -1811,29 +1833,101 @@ int qcnn_forward_u8_resized_views(QcnnCtx* c, const uint8_t* src_dev, size_t src
     if (s.offset > src_bytes || bytes > src_bytes - s.offset)
       return fail(c, "image %d: %llu bytes at offset %llu leave the source buffer of %zu bytes", i, bytes, (unsigned long long)s.offset, src_bytes);
   }
-  // every argument is good: stage the descriptors.  The last reader of the set taken — the pack kernel of the call before the
-  // previous one — must have passed before its buffers are rewritten or freed.
-  QcnnCtx::SrcStage& g = c->srcStage[c->srcStageNext];
-  c->srcStageNext ^= 1;
-  if (!g.ev) HIP_TRY(c, hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
-  if (g.used) HIP_TRY(c, hipEventSynchronize(g.ev));
-  if (g.cap < (size_t)n) {
-    if (g.pin) (void)hipHostFree(g.pin);
-    if (g.dev) (void)hipFree(g.dev);
-    g.pin = nullptr; g.dev = nullptr; g.cap = 0; g.used = false;
-    const size_t cap = std::max<size_t>((size_t)n, 64);
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&g.pin), cap * sizeof(QkSrcImage), hipHostMallocPortable));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&g.dev), cap * sizeof(QkSrcImage)));
-    g.cap = cap;
-  }
+  // every argument is good: stage the descriptors
+  QcnnCtx::SrcStage* gp = stage_take(c, (size_t)n, sizeof(QkSrcImage));
+  if (!gp) return 1;
+  QcnnCtx::SrcStage& g = *gp;
+  QkSrcImage* pin = static_cast<QkSrcImage*>(g.pin);
   for (int i = 0; i < n; ++i) {                       // the scales: one IEEE division each, as ReszImg computes them
     const QcnnSrcImage& s = imgs_host[i];
-    g.pin[i] = QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)};
+    pin[i] = QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)};
   }
   if (views_scratch(c, n, prob_dev || top5_dev)) return 1;
   g.used = true;                                      // from here on the set may be in flight
   HIP_TRY(c, hipMemcpyAsync(g.dev, g.pin, (size_t)n * sizeof(QkSrcImage), hipMemcpyHostToDevice, c->stream));
-  hipError_t e = qk_pack_u8_resized(src_dev, g.dev, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
+  hipError_t e = qk_pack_u8_resized(src_dev, static_cast<const QkSrcImage*>(g.dev), mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
+  if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
+  HIP_TRY(c, hipEventRecord(g.ev, c->stream));
+  return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_views_ten_crop_anchored(QcnnAnchorView* views10) {
+  if (!views10) return 1;
+  const int five[5][2] = {{0, 0}, {0, 2}, {2, 0}, {2, 2}, {1, 1}};
+  for (int k = 0; k < 10; ++k) views10[k] = QcnnAnchorView{five[k % 5][0], five[k % 5][1], 0, 0, k / 5};
+  return 0;
+}
+
+// BmpImgIO::ReszImg's Relaxed branch (src/BmpImgIO.cc:124-131) operation for operation: every division is a float division
+// (int / float converts the int), kEpsilon is a double, the cast truncates.  The quotient is compared in double before the cast.
+int qcnn_relaxed_full_size(int h, int w, int full_h, int full_w, int* hf, int* wf, float* scale) {
+  if (h < 2 || w < 2 || full_h < 2 || full_w < 2 || !hf || !wf) return 1;
+  const float sh = (float)(h - 1) / (float)(full_h - 1), sw = (float)(w - 1) / (float)(full_w - 1);
+  const float s = sh < sw ? sh : sw;                  // lines 127-128 leave both scales equal to the smaller
+  const double qh = (double)((float)(h - 1) / s) + 0.0000001, qw = (double)((float)(w - 1) / s) + 0.0000001;
+  if (!(qh < 16777215.0) || !(qw < 16777215.0)) return 1;     // a full size of 2^24 or more: (float)Y would not be exact
+  *hf = (int)qh + 1;
+  *wf = (int)qw + 1;
+  if (scale) *scale = s;
+  return 0;
+}
+
+int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
+                                  int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
+                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->committed) return fail(c, "model not committed");
+  if (!src_dev || !imgs_host || !views_host) return fail(c, "qcnn_forward_u8_relaxed_views: source buffer, images or views == NULL");
+  if (n <= 0) return fail(c, "batch %d: no image", n);
+  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
+  if ((long long)n * n_views > c->maxBatch)
+    return fail(c, "%d images x %d views = %lld batch slots, the model is committed for %d", n, n_views, (long long)n * n_views, c->maxBatch);
+  if (full_h < 2 || full_w < 2)
+    return fail(c, "full image %dx%d: the resize scale divides by full - 1, both sizes must be at least 2", full_h, full_w);
+  if (full_h < c->inH || full_w < c->inW)
+    return fail(c, "the full image %dx%d is smaller than the network input %dx%d", full_h, full_w, c->inH, c->inW);
+  if ((long long)c->inC * full_h * full_w > INT_MAX) return fail(c, "the full image %dx%dx%d has 2 GiB or more", c->inC, full_h, full_w);
+  QkAnchorViews views = {};
+  for (int v = 0; v < n_views; ++v) {
+    const QcnnAnchorView& q = views_host[v];
+    if (q.ay < 0 || q.ay > 2 || q.ax < 0 || q.ax > 2) return fail(c, "view %d: anchors (%d, %d) outside 0..2", v, q.ay, q.ax);
+    views.v[v] = QkAnchorView{q.ay, q.ax, q.dy, q.dx, q.flip ? 1 : 0};
+  }
+  for (int i = 0; i < n; ++i) {
+    const QcnnSrcImage& s = imgs_host[i];
+    if (s.h < 2 || s.w < 2) return fail(c, "image %d: size %dx%d, the one scale of a relaxed resize needs two pixels a side", i, s.h, s.w);
+    const unsigned long long rows = (unsigned long long)c->inC * (unsigned long long)s.h, bytes = rows * (unsigned long long)s.w;   // rows <= INT_MAX is asked first: then bytes < 2^62
+    if (rows > (unsigned long long)INT_MAX || bytes > (unsigned long long)INT_MAX)
+      return fail(c, "image %d: %dx%dx%d has 2 GiB or more (offsets inside an image are 32-bit)", i, c->inC, s.h, s.w);
+    if (s.offset > src_bytes || bytes > src_bytes - s.offset)
+      return fail(c, "image %d: %llu bytes at offset %llu leave the source buffer of %zu bytes", i, bytes, (unsigned long long)s.offset, src_bytes);
+    int hf = 0, wf = 0;
+    if (qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &hf, &wf, nullptr))
+      return fail(c, "image %d: %dx%d resized towards %dx%d has a side of 2^24 pixels or more", i, s.h, s.w, full_h, full_w);
+    for (int v = 0; v < n_views; ++v) {               // in 64 bits: d is the caller's
+      const QkAnchorView& q = views.v[v];
+      const long long oy = (((long long)(hf - c->inH) * q.ay) >> 1) + q.dy, ox = (((long long)(wf - c->inW) * q.ax) >> 1) + q.dx;
+      if (hf < c->inH || wf < c->inW || oy < 0 || ox < 0 || oy > hf - c->inH || ox > wf - c->inW)
+        return fail(c, "image %d, view %d: the %dx%d crop at (%lld, %lld) leaves the image's %dx%d full size (source %dx%d)", i, v, c->inH,
+                    c->inW, oy, ox, hf, wf, s.h, s.w);
+    }
+  }
+  // every argument is good: stage the descriptors with each image's scale and full size
+  QcnnCtx::SrcStage* gp = stage_take(c, (size_t)n, sizeof(QkRelaxedImage));
+  if (!gp) return 1;
+  QcnnCtx::SrcStage& g = *gp;
+  QkRelaxedImage* pin = static_cast<QkRelaxedImage*>(g.pin);
+  for (int i = 0; i < n; ++i) {
+    const QcnnSrcImage& s = imgs_host[i];
+    QkRelaxedImage d = {s.offset, s.h, s.w, 0.0f, 0, 0, 0};
+    (void)qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &d.hf, &d.wf, &d.s);     // succeeded above
+    pin[i] = d;
+  }
+  if (views_scratch(c, n, prob_dev || top5_dev)) return 1;
+  g.used = true;                                      // from here on the set may be in flight
+  HIP_TRY(c, hipMemcpyAsync(g.dev, g.pin, (size_t)n * sizeof(QkRelaxedImage), hipMemcpyHostToDevice, c->stream));
+  hipError_t e = qk_pack_u8_relaxed(src_dev, static_cast<const QkRelaxedImage*>(g.dev), mean_crop_dev, c->fmBuf[0], n, n_views, views,
+                                    c->inC, c->inH, c->inW, c->stream);
   if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
   HIP_TRY(c, hipEventRecord(g.ev, c->stream));
   return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);

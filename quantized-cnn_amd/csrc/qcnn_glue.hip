@@ -3,7 +3,7 @@
 // the FC layers' split partial sums, and the conversions between the reference's NCHW / row-major host layouts and the
 // 128-image panels (:1146-1160, :187-189), among them the 8-bit input pipelines (one centre crop per image, or several crops and
 // mirrors per image with the mean of their class probabilities: k_pack_u8_views, k_mean_views; the same from source images of any
-// size, resized on the way: k_pack_u8_resized).  All of them are streaming kernels bound by HBM (or, for LRN, by the
+// size, resized on the way: k_pack_u8_resized, k_pack_u8_relaxed).  All of them are streaming kernels bound by HBM (or, for LRN, by the
 // expf/logf pair); the two hot kernels live in qcnn_kernels.hip.  Feature maps are panels [pixel][channel][128 images]
 // (qcnn_kernels.h); a float4 lane carries four images.
 #include "qcnn_kernels.h"
@@ -705,6 +705,91 @@ __global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restri
   }
 }
 
+// k_pack_u8_resized for the reference's other pre-processing mode (qcnn_forward_u8_relaxed_views): BmpImgIO::ReszImg Relaxed —
+// ONE scale s for both axes, so image i has its own full size hf x wf (both computed by the engine on the host with the
+// reference's float sequence and staged with the descriptor, QkRelaxedImage) — then CropImg and a mean of the CROP's size
+// (ENUM_MeanType::Crop, src/BmpImgIO.cc:56-64,124-131).  Per (slot, element) the value is the resized kernel's with sh = sw = s:
+//   (((p00 * w00 + p01 * w01) + p10 * w10) + p11 * w11) / (((w00 + w01) + w10) + w11) - mean[c][y][xl]
+// at the full-image position (Y, X) = (oy + y, ox + xl), xl = x or the mirrored column, and what differs is where the slot
+// part comes from:
+//   * the view corner is resolved per slot from the view's anchor and ITS image's full size, wave-uniformly, in scalar
+//     registers: o = (((full - in) * a) >> 1) + d, which is 0, CropImg's (full - in) / 2 and full - in for a = 0, 1, 2 (full >= in:
+//     the engine checked every view against every image);
+//   * the mean is indexed by the element alone (view-local position BEFORE mirroring), so its loads leave the slot loop: two
+//     per thread per block — the plain and the mirrored column, a slot picks by its wave-uniform flip — where the resized
+//     kernel issues one per slot.
+// Everything else is k_pack_u8_resized: the 128-slot x 64-element LDS transpose, unconditional loads (a dead slot reads image 0
+// under its view, which the engine checked like every other pair; taps are clamped into the image besides), eight slots a
+// round with their 32 tap loads in flight before the first is waited for, descriptor and view through scalar loads, 32-bit
+// offsets inside an image, one rounding per operation.
+template <bool MEAN>
+__global__ __launch_bounds__(256) void k_pack_u8_relaxed(const uint8_t* __restrict__ in, const QkRelaxedImage* __restrict__ desc,
+                                                         const float* __restrict__ mean, float* __restrict__ dst, int S, int V,
+                                                         const QkAnchorViews views, int C, int H, int W) {
+  __shared__ float tile[PANEL][65];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int HW = H * W, E = C * HW;
+  const int e0 = blockIdx.x * 64;
+  const int panel = blockIdx.y;
+  const int e = e0 + lane;
+  const int el = e < E ? e : 0;                     // the element whose source positions this thread reads
+  const int ey = (el % HW) / W;                     // its row in a view
+  const int ex0 = el % W, ex1 = W - 1 - el % W;     // its column in a plain / a mirrored view
+  const unsigned ch = el / HW;                      // its channel
+  const float mPlain = MEAN ? mean[el] : 0.0f;      // mean[c][ey][ex0]: el = (c * H + ey) * W + ex0
+  const float mFlip = MEAN ? mean[el - ex0 + ex1] : 0.0f;
+  const int q4 = 4 / V, r4 = 4 % V;                 // the wave's next slot is four further: q4 images and r4 views
+  int img = (panel * PANEL + wave) / V, vw = (panel * PANEL + wave) % V;
+  constexpr int R = 8;                              // slots a round
+#pragma unroll
+  for (int b = 0; b < PANEL / 4; b += R) {
+    uint8_t p00[R], p01[R], p10[R], p11[R];
+    float w00[R], w01[R], w10[R], w11[R];
+    bool flip[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const bool liveSlot = panel * PANEL + wave + 4 * (b + u) < S;     // wave-uniform
+      const QkRelaxedImage d = desc[liveSlot ? img : 0];
+      const QkAnchorView q = views.v[vw];           // vw < V <= QK_MAX_VIEWS also for the dead slots of a ragged panel
+      const int oy = (((d.hf - H) * q.ay) >> 1) + q.dy, ox = (((d.wf - W) * q.ax) >> 1) + q.dx;
+      flip[u] = q.flip != 0;
+      const int Y = oy + ey, X = ox + (flip[u] ? ex1 : ex0);            // < hf, < wf: the engine checked view x image
+      const float yc = __fmul_rn(d.s, (float)Y), xc = __fmul_rn(d.s, (float)X);
+      const int y0 = min(max(0, (int)yc), d.h - 1), x0 = min(max(0, (int)xc), d.w - 1);
+      const int y1 = min(d.h - 1, y0 + 1), x1 = min(d.w - 1, x0 + 1);
+      const float wy0 = __fsub_rn(1.0f, __fsub_rn(yc, (float)y0)), wy1 = __fsub_rn(1.0f, __fsub_rn((float)y1, yc));
+      const float wx0 = __fsub_rn(1.0f, __fsub_rn(xc, (float)x0)), wx1 = __fsub_rn(1.0f, __fsub_rn((float)x1, xc));
+      w00[u] = __fmul_rn(wy0, wx0); w01[u] = __fmul_rn(wy0, wx1); w10[u] = __fmul_rn(wy1, wx0); w11[u] = __fmul_rn(wy1, wx1);
+      const uint8_t* px = in + d.off;
+      const unsigned r0 = (ch * d.h + y0) * d.w, r1 = (ch * d.h + y1) * d.w;   // < C * h * w <= INT_MAX
+      p00[u] = px[r0 + x0]; p01[u] = px[r0 + x1]; p10[u] = px[r1 + x0]; p11[u] = px[r1 + x1];
+      img += q4;
+      vw += r4;
+      if (vw >= V) { vw -= V; ++img; }
+    }
+    __builtin_amdgcn_sched_barrier(0);              // every load of the round is issued before the first value is waited for
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const bool live = panel * PANEL + wave + 4 * (b + u) < S && e < E;
+      const float num = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn((float)p00[u], w00[u]), __fmul_rn((float)p01[u], w01[u])),
+                                            __fmul_rn((float)p10[u], w10[u])), __fmul_rn((float)p11[u], w11[u]));
+      const float den = __fadd_rn(__fadd_rn(__fadd_rn(w00[u], w01[u]), w10[u]), w11[u]);
+      const float val = __fdiv_rn(num, den);
+      tile[wave + 4 * (b + u)][lane] = live ? (MEAN ? __fsub_rn(val, flip[u] ? mFlip : mPlain) : val) : 0.0f;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
+  for (int j = wave; j < 64; j += 4) {
+    const int ee = e0 + j;
+    if (ee < E) {
+      const int c = ee / HW, hw = ee % HW;
+      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)hw * C + c) * PANEL + 2 * lane) =
+          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
+    }
+  }
+}
+
 // Class probabilities of n * V slots -> their mean over the V views of each of n images, both in panels [C][128]: one thread =
 // one (image, class), s = p[view 0]; s = s + p[view v] in view order; s / (float)V, every operation rounded once (V = 1: the
 // row itself).  The slots of an image are neighbours but may lie on both sides of a panel seam; an image's lane of the output
@@ -904,6 +989,17 @@ hipError_t qk_pack_u8_resized(const uint8_t* in, const QkSrcImage* desc, const f
   const int E = C * H * W, S = n * V;
   hipLaunchKernelGGL(mean ? k_pack_u8_resized<true> : k_pack_u8_resized<false>, dim3((E + 63) / 64, panels_of(S)), dim3(256), 0,
                      st, in, desc, mean, dst, S, V, views, C, H, W, Hf, Wf);
+  return hipGetLastError();
+}
+
+hipError_t qk_pack_u8_relaxed(const uint8_t* in, const QkRelaxedImage* desc, const float* mean, float* dst, int n, int V,
+                              const QkAnchorViews& views, int C, int H, int W, hipStream_t st) {
+  if (n <= 0 || V < 1 || V > QK_MAX_VIEWS || !in || !desc || C < 1 || H < 1 || W < 1) return hipErrorInvalidValue;
+  for (int v = 0; v < V; ++v)                       // an anchor outside 0..2 must never reach the kernel
+    if (views.v[v].ay < 0 || views.v[v].ay > 2 || views.v[v].ax < 0 || views.v[v].ax > 2) return hipErrorInvalidValue;
+  const int E = C * H * W, S = n * V;
+  hipLaunchKernelGGL(mean ? k_pack_u8_relaxed<true> : k_pack_u8_relaxed<false>, dim3((E + 63) / 64, panels_of(S)), dim3(256), 0,
+                     st, in, desc, mean, dst, S, V, views, C, H, W);
   return hipGetLastError();
 }
 

@@ -445,6 +445,22 @@ struct QkSrcImage { unsigned long long off; int h, w; float sh, sw; };
 // checked every descriptor against the source buffer (h, w >= 1, C * h * w <= INT_MAX, inside the buffer).
 hipError_t qk_pack_u8_resized(const uint8_t* in, const QkSrcImage* desc, const float* mean, float* dst, int n, int V,
                               const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st);
+// A source image of qcnn_forward_u8_relaxed_views (BmpImgIO::ReszImg, Relaxed) as the kernel reads it from the staged table:
+// the QcnnSrcImage, the ONE scale s = min(sh, sw) of both axes and the image's own full size hf x wf — all three computed once
+// per image on the host with the reference's float sequence (qcnn_relaxed_full_size).  A struct of its own: QkSrcImage keeps
+// its 24 bytes, and with them k_pack_u8_resized its code.
+struct QkRelaxedImage { unsigned long long off; int h, w; float s; int hf, wf, pad; };
+// The views of qcnn_forward_u8_relaxed_views, by value like QkViews.  Same fields as QcnnAnchorView (include/qcnn_hip.h): the
+// kernel resolves the corner of a slot from its image's hf x wf, o = (((full - in) * a) >> 1) + d; the engine checked every
+// (image, view) pair.
+struct QkAnchorView { int ay, ax, dy, dx, flip; };
+struct QkAnchorViews { QkAnchorView v[QK_MAX_VIEWS]; };
+// 8-bit planar images [C][h_i][w_i] at in + desc[i].off, each resized by its one scale to hf_i x wf_i, -> panels [H*W*C][128]
+// of n * V slots: slot i * V + v = the H x W crop of resized image i at the corner views.v[v] resolves to, minus mean [C][H][W]
+// (or NULL) at the view-local position, then mirrored left-right where .flip (lanes >= n * V zero-filled).  desc [n] in DEVICE
+// memory; the caller checked every descriptor against the source buffer and every view against every image's hf x wf.
+hipError_t qk_pack_u8_relaxed(const uint8_t* in, const QkRelaxedImage* desc, const float* mean, float* dst, int n, int V,
+                              const QkAnchorViews& views, int C, int H, int W, hipStream_t st);
 // panels [C][128] of n * V slots -> panels [C][128] of n images: the mean over the V slots of an image, summed in slot order
 // in fp32 and divided by (float)V (lanes >= n zero-filled)
 hipError_t qk_mean_views(const float* src, float* dst, int n, int V, int C, hipStream_t st);

@@ -302,6 +302,57 @@ class QcnnEngine:
         self.sync()
         return d_prob.cpu().numpy(), d_top5.cpu().numpy().view(np.uint16), d_rows.cpu().numpy()
 
+    def forward_u8_relaxed_views_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int, mean_crop_ptr: int | None,
+                                     views, prob_ptr: int | None = None, top5_ptr: int | None = None,
+                                     prob_views_ptr: int | None = None):
+        """Asynchronous, device pointers: multi-view inference from 8-bit planar images of ANY size in the reference's Relaxed /
+        Crop mode (qcnn_forward_u8_relaxed_views; VggCnnS): each image resized by one scale towards full_h x full_w — its full
+        size is its own, relaxed_full_size gives it — cropped, a mean of the crop's size subtracted.  descs as
+        forward_u8_resized_views_dev takes them; mean_crop [C][in_h][in_w] or None; views: a sequence of (ay, ax, dy, dx, flip)
+        (ten_crop_anchored gives the standard ten; (1, 1, 0, 0, 0) is BmpImgIO's centre crop).  Neither list has to outlive
+        the call."""
+        if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcImage:     # made once by the caller: no per-call conversion
+            darr, n = descs, len(descs)
+        else:
+            ds = [tuple(int(x) for x in d) for d in descs]
+            darr, n = (capi.QcnnSrcImage * max(len(ds), 1))(*[capi.QcnnSrcImage(*d) for d in ds]), len(ds)
+        vs = [tuple(int(x) for x in v) for v in views]
+        varr = (capi.QcnnAnchorView * max(len(vs), 1))(*[capi.QcnnAnchorView(*v) for v in vs])
+        self._chk(self.lib.qcnn_forward_u8_relaxed_views(self.h, C.c_void_p(src_ptr), src_bytes, darr, n, full_h, full_w,
+                                                         C.c_void_p(mean_crop_ptr) if mean_crop_ptr else None, varr, len(vs),
+                                                         C.c_void_p(prob_ptr) if prob_ptr else None,
+                                                         C.c_void_p(top5_ptr) if top5_ptr else None,
+                                                         C.c_void_p(prob_views_ptr) if prob_views_ptr else None))
+
+    def forward_u8_relaxed_host(self, images, full_hw, mean_crop=None, views=None):
+        """Blocking convenience: images — a list of uint8 arrays [C][h][w] of differing sizes — are packed, uploaded, resized
+        by one scale each towards full_hw = (full_h, full_w) on the device, cropped, the float32 mean_crop [C][in_h][in_w] (or
+        None) subtracted, and evaluated on `views` (default: the centre anchor alone, which makes the call BmpImgIO::Load of a
+        Relaxed / Crop model + the forward pass).  Returns (prob [n][classes] averaged over the views, top5 [n][5], prob_views
+        [n][len(views)][classes]) as numpy arrays."""
+        import torch   # plumbing only: device buffers and copies
+        full_h, full_w = int(full_hw[0]), int(full_hw[1])
+        if views is None:
+            views = [(1, 1, 0, 0, 0)]
+        flat, descs = pack_sources(images)
+        n, V = len(descs), len(views)
+        fh, fw, fc = self.fm_dims(self.L)
+        classes = fh * fw * fc
+        dev = torch.device("cuda", self.lib.qcnn_ctx_device(self.h))
+        d_src = torch.from_numpy(flat).to(dev)
+        d_mean = torch.from_numpy(np.ascontiguousarray(mean_crop, np.float32)).to(dev) if mean_crop is not None else None
+        if d_mean is not None and tuple(d_mean.shape) != tuple(self.in_chw):
+            raise QcnnError("crop mean %r, expected %r" % (tuple(d_mean.shape), tuple(self.in_chw)))
+        d_prob = torch.empty((n, classes), dtype=torch.float32, device=dev)
+        d_top5 = torch.empty((n, 5), dtype=torch.int16, device=dev)
+        d_rows = torch.empty((n, max(V, 1), classes), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.forward_u8_relaxed_views_dev(d_src.data_ptr(), flat.size, descs, full_h, full_w,
+                                          d_mean.data_ptr() if d_mean is not None else None, views,
+                                          d_prob.data_ptr(), d_top5.data_ptr(), d_rows.data_ptr())
+        self.sync()
+        return d_prob.cpu().numpy(), d_top5.cpu().numpy().view(np.uint16), d_rows.cpu().numpy()
+
     def forward_host(self, imgs_nchw, want_prob=True, want_top5=True):
         imgs = np.ascontiguousarray(imgs_nchw, np.float32)
         n = imgs.shape[0]
@@ -392,6 +443,26 @@ def ten_crop_views(src_h: int, src_w: int, in_h: int, in_w: int):
     if lib.qcnn_views_ten_crop(src_h, src_w, in_h, in_w, arr):
         raise QcnnError("ten_crop_views: a %dx%d source holds no %dx%d crop" % (src_h, src_w, in_h, in_w))
     return [(v.oy, v.ox, v.flip) for v in arr]
+
+
+def ten_crop_anchored():
+    """The standard ten views as anchors [(ay, ax, dy, dx, flip)] for forward_u8_relaxed_views_dev (qcnn_views_ten_crop_anchored):
+    four corners, centre, then their mirrors, each resolved against every image's own full size.  Needs no device."""
+    lib = capi.load()
+    arr = (capi.QcnnAnchorView * 10)()
+    if lib.qcnn_views_ten_crop_anchored(arr):
+        raise QcnnError("ten_crop_anchored failed")
+    return [(v.ay, v.ax, v.dy, v.dx, v.flip) for v in arr]
+
+
+def relaxed_full_size(h: int, w: int, full_h: int, full_w: int):
+    """(Hf, Wf, scale) of an h x w source resized towards full_h x full_w by the reference's Relaxed rule
+    (qcnn_relaxed_full_size): its float arithmetic, which can land one pixel under the nominal size.  Needs no device."""
+    lib = capi.load()
+    hf, wf, s = C.c_int(), C.c_int(), C.c_float()
+    if lib.qcnn_relaxed_full_size(int(h), int(w), int(full_h), int(full_w), C.byref(hf), C.byref(wf), C.byref(s)):
+        raise QcnnError("relaxed_full_size: %dx%d towards %dx%d is refused (a side under 2, or a full size of 2^24 or more)" % (h, w, full_h, full_w))
+    return hf.value, wf.value, np.float32(s.value)
 
 
 def pack_sources(images):
