@@ -1674,21 +1674,25 @@ int qcnn_fm_dims(QcnnCtx* c, int l, int* hwc3) {
 }
 
 namespace {
-// layers + output conversion of a forward whose input panel (fmBuf[0]) has just been enqueued
-// output conversion of a finished layer loop: probabilities [n][classes], top-5 [n][5]
-int forward_outputs(QcnnCtx* c, int n, float* prob_dev, uint16_t* top5_dev) {
+// output conversion of a map of panels [classes][128]: probabilities [n][classes], top-5 [n][5]
+int map_outputs(QcnnCtx* c, const float* map, int n, float* prob_dev, uint16_t* top5_dev) {
   const int classes = (int)fm_elems(c, c->L);
   hipError_t e;
   if (prob_dev) {
-    e = qk_unpack_rows(c->lastFm[c->L], prob_dev, n, classes, c->stream);
+    e = qk_unpack_rows(map, prob_dev, n, classes, c->stream);
     if (e != hipSuccess) return fail(c, "output unpack launch failed: %s", hipGetErrorString(e));
   }
   if (top5_dev) {
-    e = qk_top5(c->lastFm[c->L], top5_dev, n, classes, c->stream);
+    e = qk_top5(map, top5_dev, n, classes, c->stream);
     if (e != hipSuccess) return fail(c, "top-5 launch failed: %s", hipGetErrorString(e));
   }
   return 0;
 }
+// output conversion of a finished layer loop
+int forward_outputs(QcnnCtx* c, int n, float* prob_dev, uint16_t* top5_dev) {
+  return map_outputs(c, c->lastFm[c->L], n, prob_dev, top5_dev);
+}
+// layers + output conversion of a forward whose input panel (fmBuf[0]) has just been enqueued
 int forward_tail(QcnnCtx* c, int n, float* prob_dev, uint16_t* top5_dev, const float* inNchw = nullptr) {
   if (run_layers(c, n, inNchw)) return 1;
   return forward_outputs(c, n, prob_dev, top5_dev);
@@ -1763,39 +1767,79 @@ QcnnCtx::SrcStage* stage_take(QcnnCtx* c, size_t n, size_t each) {
   return &g;
 }
 int views_tail(QcnnCtx* c, int n, int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  const int slots = n * n_views, classes = (int)fm_elems(c, c->L);
-  if (forward_tail(c, slots, prob_views_dev, nullptr)) return 1;     // the un-averaged rows: one per slot
+  if (forward_tail(c, n * n_views, prob_views_dev, nullptr)) return 1;     // the un-averaged rows: one per slot
   if (!prob_dev && !top5_dev) return 0;
-  hipError_t e = qk_mean_views(c->lastFm[c->L], c->viewMean, n, n_views, classes, c->stream);
+  hipError_t e = qk_mean_views(c->lastFm[c->L], c->viewMean, n, n_views, (int)fm_elems(c, c->L), c->stream);
   if (e != hipSuccess) return fail(c, "view mean launch failed: %s", hipGetErrorString(e));
-  if (prob_dev) {
-    e = qk_unpack_rows(c->viewMean, prob_dev, n, classes, c->stream);
-    if (e != hipSuccess) return fail(c, "output unpack launch failed: %s", hipGetErrorString(e));
+  return map_outputs(c, c->viewMean, n, prob_dev, top5_dev);
+}
+
+// What every multi-view call asks first.  `missing`: what the NULL message names, nullptr when every pointer is there.
+int views_open(QcnnCtx* c, const char* fn, const char* missing, int n, int n_views) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->committed) return fail(c, "model not committed");
+  if (missing) return fail(c, "%s: %s == NULL", fn, missing);
+  if (n <= 0) return fail(c, "batch %d: no image", n);
+  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
+  if ((long long)n * n_views > c->maxBatch)
+    return fail(c, "%d images x %d views = %lld batch slots, the model is committed for %d", n, n_views, (long long)n * n_views, c->maxBatch);
+  return 0;
+}
+// The views of a call as the kernels take them, each crop inside the h x w image (`which`: source or full) it is cut from.
+int crop_views(QcnnCtx* c, const QcnnView* views_host, int n_views, int h, int w, const char* which, QkViews* views) {
+  for (int v = 0; v < n_views; ++v) {
+    const QcnnView& q = views_host[v];
+    if (q.oy < 0 || q.ox < 0 || q.oy > h - c->inH || q.ox > w - c->inW)
+      return fail(c, "view %d: the %dx%d crop at (%d, %d) leaves the %dx%d %s image", v, c->inH, c->inW, q.oy, q.ox, h, w, which);
+    views->v[v] = QkView{q.oy, q.ox, q.flip ? 1 : 0};
   }
-  if (top5_dev) {
-    e = qk_top5(c->viewMean, top5_dev, n, classes, c->stream);
-    if (e != hipSuccess) return fail(c, "top-5 launch failed: %s", hipGetErrorString(e));
-  }
+  return 0;
+}
+// The full image of a resize: what its scale, the network input and 32-bit offsets need.
+int full_image_ok(QcnnCtx* c, int full_h, int full_w) {
+  if (full_h < 2 || full_w < 2)
+    return fail(c, "full image %dx%d: the resize scale divides by full - 1, both sizes must be at least 2", full_h, full_w);
+  if (full_h < c->inH || full_w < c->inW)
+    return fail(c, "the full image %dx%d is smaller than the network input %dx%d", full_h, full_w, c->inH, c->inW);
+  if ((long long)c->inC * full_h * full_w > INT_MAX) return fail(c, "the full image %dx%dx%d has 2 GiB or more", c->inC, full_h, full_w);
+  return 0;
+}
+// Source image i: its sides (at least 1 for a Strict, 2 for a Relaxed resize), its size, its place in the source buffer.
+int src_image_ok(QcnnCtx* c, int i, const QcnnSrcImage& s, size_t src_bytes, int minSide) {
+  if (s.h < minSide || s.w < minSide)
+    return minSide < 2 ? fail(c, "image %d: size %dx%d", i, s.h, s.w)
+                       : fail(c, "image %d: size %dx%d, the one scale of a relaxed resize needs two pixels a side", i, s.h, s.w);
+  const unsigned long long rows = (unsigned long long)c->inC * (unsigned long long)s.h, bytes = rows * (unsigned long long)s.w;   // rows <= INT_MAX is asked first: then bytes < 2^62
+  if (rows > (unsigned long long)INT_MAX || bytes > (unsigned long long)INT_MAX)
+    return fail(c, "image %d: %dx%dx%d has 2 GiB or more (offsets inside an image are 32-bit)", i, c->inC, s.h, s.w);
+  if (s.offset > src_bytes || bytes > src_bytes - s.offset)
+    return fail(c, "image %d: %llu bytes at offset %llu leave the source buffer of %zu bytes", i, bytes, (unsigned long long)s.offset, src_bytes);
+  return 0;
+}
+// Stage n descriptors D — fill(i) makes image i's — and launch the pack kernel that reads them.  Called when every argument
+// is good: nothing is taken or rewritten for a call that is refused.  The set is marked in flight only once nothing of the
+// host's can fail any more, and its event is recorded behind its one reader.
+extern "C++" template <class D, class Fill, class Launch>
+int stage_and_pack(QcnnCtx* c, int n, bool wantMean, Fill fill, Launch launch) {
+  QcnnCtx::SrcStage* g = stage_take(c, (size_t)n, sizeof(D));
+  if (!g) return 1;
+  D* pin = static_cast<D*>(g->pin);
+  for (int i = 0; i < n; ++i) pin[i] = fill(i);
+  if (views_scratch(c, n, wantMean)) return 1;
+  g->used = true;                                     // from here on the set may be in flight
+  HIP_TRY(c, hipMemcpyAsync(g->dev, g->pin, (size_t)n * sizeof(D), hipMemcpyHostToDevice, c->stream));
+  hipError_t e = launch(static_cast<const D*>(g->dev));
+  if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
+  HIP_TRY(c, hipEventRecord(g->ev, c->stream));
   return 0;
 }
 }  // namespace
 
 int qcnn_forward_u8_views(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int src_w, const float* mean_dev, int n,
                           const QcnnView* views_host, int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->committed) return fail(c, "model not committed");
-  if (!in_u8_dev || !views_host) return fail(c, "qcnn_forward_u8_views: images or views == NULL");
-  if (n <= 0) return fail(c, "batch %d: no image", n);
-  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
-  if ((long long)n * n_views > c->maxBatch)
-    return fail(c, "%d images x %d views = %lld batch slots, the model is committed for %d", n, n_views, (long long)n * n_views, c->maxBatch);
+  if (views_open(c, "qcnn_forward_u8_views", in_u8_dev && views_host ? nullptr : "images or views", n, n_views)) return 1;
   QkViews views = {};
-  for (int v = 0; v < n_views; ++v) {
-    const QcnnView& q = views_host[v];
-    if (q.oy < 0 || q.ox < 0 || q.oy > src_h - c->inH || q.ox > src_w - c->inW)
-      return fail(c, "view %d: the %dx%d crop at (%d, %d) leaves the %dx%d source image", v, c->inH, c->inW, q.oy, q.ox, src_h, src_w);
-    views.v[v] = QkView{q.oy, q.ox, q.flip ? 1 : 0};
-  }
+  if (crop_views(c, views_host, n_views, src_h, src_w, "source", &views)) return 1;
   if (views_scratch(c, n, prob_dev || top5_dev)) return 1;
   hipError_t e = qk_pack_u8_views(in_u8_dev, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, src_h, src_w, c->stream);
   if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
@@ -1805,49 +1849,23 @@ int qcnn_forward_u8_views(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int s
 int qcnn_forward_u8_resized_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
                                   int full_h, int full_w, const float* mean_dev, const QcnnView* views_host, int n_views,
                                   float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->committed) return fail(c, "model not committed");
-  if (!src_dev || !imgs_host || !views_host) return fail(c, "qcnn_forward_u8_resized_views: source buffer, images or views == NULL");
-  if (n <= 0) return fail(c, "batch %d: no image", n);
-  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
-  if ((long long)n * n_views > c->maxBatch)
-    return fail(c, "%d images x %d views = %lld batch slots, the model is committed for %d", n, n_views, (long long)n * n_views, c->maxBatch);
-  if (full_h < 2 || full_w < 2)
-    return fail(c, "full image %dx%d: the resize scale divides by full - 1, both sizes must be at least 2", full_h, full_w);
-  if (full_h < c->inH || full_w < c->inW)
-    return fail(c, "the full image %dx%d is smaller than the network input %dx%d", full_h, full_w, c->inH, c->inW);
-  if ((long long)c->inC * full_h * full_w > INT_MAX) return fail(c, "the full image %dx%dx%d has 2 GiB or more", c->inC, full_h, full_w);
+  if (views_open(c, "qcnn_forward_u8_resized_views", src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views",
+                 n, n_views) || full_image_ok(c, full_h, full_w))
+    return 1;
   QkViews views = {};
-  for (int v = 0; v < n_views; ++v) {
-    const QcnnView& q = views_host[v];
-    if (q.oy < 0 || q.ox < 0 || q.oy > full_h - c->inH || q.ox > full_w - c->inW)
-      return fail(c, "view %d: the %dx%d crop at (%d, %d) leaves the %dx%d full image", v, c->inH, c->inW, q.oy, q.ox, full_h, full_w);
-    views.v[v] = QkView{q.oy, q.ox, q.flip ? 1 : 0};
-  }
-  for (int i = 0; i < n; ++i) {
-    const QcnnSrcImage& s = imgs_host[i];
-    if (s.h < 1 || s.w < 1) return fail(c, "image %d: size %dx%d", i, s.h, s.w);
-    const unsigned long long rows = (unsigned long long)c->inC * (unsigned long long)s.h, bytes = rows * (unsigned long long)s.w;   // rows <= INT_MAX is asked first: then bytes < 2^62
-    if (rows > (unsigned long long)INT_MAX || bytes > (unsigned long long)INT_MAX)
-      return fail(c, "image %d: %dx%dx%d has 2 GiB or more (offsets inside an image are 32-bit)", i, c->inC, s.h, s.w);
-    if (s.offset > src_bytes || bytes > src_bytes - s.offset)
-      return fail(c, "image %d: %llu bytes at offset %llu leave the source buffer of %zu bytes", i, bytes, (unsigned long long)s.offset, src_bytes);
-  }
-  // every argument is good: stage the descriptors
-  QcnnCtx::SrcStage* gp = stage_take(c, (size_t)n, sizeof(QkSrcImage));
-  if (!gp) return 1;
-  QcnnCtx::SrcStage& g = *gp;
-  QkSrcImage* pin = static_cast<QkSrcImage*>(g.pin);
-  for (int i = 0; i < n; ++i) {                       // the scales: one IEEE division each, as ReszImg computes them
-    const QcnnSrcImage& s = imgs_host[i];
-    pin[i] = QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)};
-  }
-  if (views_scratch(c, n, prob_dev || top5_dev)) return 1;
-  g.used = true;                                      // from here on the set may be in flight
-  HIP_TRY(c, hipMemcpyAsync(g.dev, g.pin, (size_t)n * sizeof(QkSrcImage), hipMemcpyHostToDevice, c->stream));
-  hipError_t e = qk_pack_u8_resized(src_dev, static_cast<const QkSrcImage*>(g.dev), mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
-  if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
-  HIP_TRY(c, hipEventRecord(g.ev, c->stream));
+  if (crop_views(c, views_host, n_views, full_h, full_w, "full", &views)) return 1;
+  for (int i = 0; i < n; ++i)
+    if (src_image_ok(c, i, imgs_host[i], src_bytes, 1)) return 1;
+  if (stage_and_pack<QkSrcImage>(
+          c, n, prob_dev || top5_dev,
+          [&](int i) {                                // the scales: one IEEE division each, as ReszImg computes them
+            const QcnnSrcImage& s = imgs_host[i];
+            return QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)};
+          },
+          [&](const QkSrcImage* desc) {
+            return qk_pack_u8_resized(src_dev, desc, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
+          }))
+    return 1;
   return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
@@ -1875,18 +1893,9 @@ int qcnn_relaxed_full_size(int h, int w, int full_h, int full_w, int* hf, int* w
 int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
                                   int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
                                   float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->committed) return fail(c, "model not committed");
-  if (!src_dev || !imgs_host || !views_host) return fail(c, "qcnn_forward_u8_relaxed_views: source buffer, images or views == NULL");
-  if (n <= 0) return fail(c, "batch %d: no image", n);
-  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
-  if ((long long)n * n_views > c->maxBatch)
-    return fail(c, "%d images x %d views = %lld batch slots, the model is committed for %d", n, n_views, (long long)n * n_views, c->maxBatch);
-  if (full_h < 2 || full_w < 2)
-    return fail(c, "full image %dx%d: the resize scale divides by full - 1, both sizes must be at least 2", full_h, full_w);
-  if (full_h < c->inH || full_w < c->inW)
-    return fail(c, "the full image %dx%d is smaller than the network input %dx%d", full_h, full_w, c->inH, c->inW);
-  if ((long long)c->inC * full_h * full_w > INT_MAX) return fail(c, "the full image %dx%dx%d has 2 GiB or more", c->inC, full_h, full_w);
+  if (views_open(c, "qcnn_forward_u8_relaxed_views", src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views",
+                 n, n_views) || full_image_ok(c, full_h, full_w))
+    return 1;
   QkAnchorViews views = {};
   for (int v = 0; v < n_views; ++v) {
     const QcnnAnchorView& q = views_host[v];
@@ -1895,12 +1904,7 @@ int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src
   }
   for (int i = 0; i < n; ++i) {
     const QcnnSrcImage& s = imgs_host[i];
-    if (s.h < 2 || s.w < 2) return fail(c, "image %d: size %dx%d, the one scale of a relaxed resize needs two pixels a side", i, s.h, s.w);
-    const unsigned long long rows = (unsigned long long)c->inC * (unsigned long long)s.h, bytes = rows * (unsigned long long)s.w;   // rows <= INT_MAX is asked first: then bytes < 2^62
-    if (rows > (unsigned long long)INT_MAX || bytes > (unsigned long long)INT_MAX)
-      return fail(c, "image %d: %dx%dx%d has 2 GiB or more (offsets inside an image are 32-bit)", i, c->inC, s.h, s.w);
-    if (s.offset > src_bytes || bytes > src_bytes - s.offset)
-      return fail(c, "image %d: %llu bytes at offset %llu leave the source buffer of %zu bytes", i, bytes, (unsigned long long)s.offset, src_bytes);
+    if (src_image_ok(c, i, s, src_bytes, 2)) return 1;
     int hf = 0, wf = 0;
     if (qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &hf, &wf, nullptr))
       return fail(c, "image %d: %dx%d resized towards %dx%d has a side of 2^24 pixels or more", i, s.h, s.w, full_h, full_w);
@@ -1912,24 +1916,18 @@ int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src
                     c->inW, oy, ox, hf, wf, s.h, s.w);
     }
   }
-  // every argument is good: stage the descriptors with each image's scale and full size
-  QcnnCtx::SrcStage* gp = stage_take(c, (size_t)n, sizeof(QkRelaxedImage));
-  if (!gp) return 1;
-  QcnnCtx::SrcStage& g = *gp;
-  QkRelaxedImage* pin = static_cast<QkRelaxedImage*>(g.pin);
-  for (int i = 0; i < n; ++i) {
-    const QcnnSrcImage& s = imgs_host[i];
-    QkRelaxedImage d = {s.offset, s.h, s.w, 0.0f, 0, 0, 0};
-    (void)qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &d.hf, &d.wf, &d.s);     // succeeded above
-    pin[i] = d;
-  }
-  if (views_scratch(c, n, prob_dev || top5_dev)) return 1;
-  g.used = true;                                      // from here on the set may be in flight
-  HIP_TRY(c, hipMemcpyAsync(g.dev, g.pin, (size_t)n * sizeof(QkRelaxedImage), hipMemcpyHostToDevice, c->stream));
-  hipError_t e = qk_pack_u8_relaxed(src_dev, static_cast<const QkRelaxedImage*>(g.dev), mean_crop_dev, c->fmBuf[0], n, n_views, views,
-                                    c->inC, c->inH, c->inW, c->stream);
-  if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
-  HIP_TRY(c, hipEventRecord(g.ev, c->stream));
+  if (stage_and_pack<QkRelaxedImage>(
+          c, n, prob_dev || top5_dev,
+          [&](int i) {                                // each image's scale and full size
+            const QcnnSrcImage& s = imgs_host[i];
+            QkRelaxedImage d = {s.offset, s.h, s.w, 0.0f, 0, 0, 0};
+            (void)qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &d.hf, &d.wf, &d.s);     // succeeded above
+            return d;
+          },
+          [&](const QkRelaxedImage* desc) {
+            return qk_pack_u8_relaxed(src_dev, desc, mean_crop_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, c->stream);
+          }))
+    return 1;
   return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
 }
 

@@ -481,8 +481,86 @@ __global__ void k_top5(const float* __restrict__ prob, uint16_t* __restrict__ ou
   }
 }
 
-// [n][E] rows -> panels [E][128] through a 128 x 64 LDS tile (both sides coalesced).
-// NCHW: input element e = (c*H + h)*W + w of an image lands in row (h*W + w)*C + c (src/CaffeEva.cc:1146-1160).
+// ---- the pack kernels: rows or 8-bit images -> panels [E][128] through a 128-slot x 64-element LDS tile (both sides
+// coalesced).  One block = 64 elements of one panel; wave w fills tile rows w, w + 4, ...; the shared pieces first. ----
+// The tile's write-out: element e0 + j of all 128 slots goes to panel row rowOf(e0 + j), two slots a lane.  rowOf is called
+// before the tile is read and its result converted to the row behind the reads: what a mapping does where is its own choice.
+template <class RowOf>
+__device__ __forceinline__ void tile_write_out(const float (&tile)[PANEL][65], float* __restrict__ dst, int panel, int e0, int E,
+                                               int lane, int wave, RowOf rowOf) {
+  for (int j = wave; j < 64; j += 4) {
+    const int e = e0 + j;
+    if (e < E) {
+      const auto row = rowOf(e);
+      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)row) * PANEL + 2 * lane) =
+          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
+    }
+  }
+}
+
+// NCHW: input element e = (c*H + h)*W + w of an image lands in row (h*W + w)*C + c (src/CaffeEva.cc:1146-1160).  The division
+// is done at the call, the 64-bit product at the conversion: the tile's reads are issued between the two.
+struct NchwRow {
+  int C, HW;
+  struct Row { int c, hw, C; __device__ __forceinline__ explicit operator size_t() const { return (size_t)hw * C + c; } };
+  __device__ __forceinline__ Row operator()(int e) const { return Row{e / HW, e % HW, C}; }
+};
+
+// The slots of a multi-view panel as one wave meets them: S = n * V batch slots, slot s = view s % V of image s / V; the wave
+// starts at slot `first` = panel * 128 + wave and its next slot is four further: q4 images and r4 views, without a division
+// per slot.  Everything here is wave-uniform (`wave` is readfirstlane'd by the kernels): image, view and what is read under
+// them — descriptor, view entry — live in scalar registers and come through scalar loads.  vw < V <= QK_MAX_VIEWS also for
+// the dead slots of a ragged panel, so the view table is never read outside.  next() wraps by two selects, no branch.
+struct SlotWalk {
+  int q4, r4, img, vw, V, first, S;
+  __device__ __forceinline__ SlotWalk(int panel, int wave, int V_, int S_)       // in this order: q4 and r4 are worked out first
+      : q4(4 / V_), r4(4 % V_), img((panel * PANEL + wave) / V_), vw((panel * PANEL + wave) % V_), V(V_), first(panel * PANEL + wave), S(S_) {}
+  __device__ __forceinline__ void next() {
+    img += q4;
+    vw += r4;
+    const bool wrap = vw >= V;
+    vw -= wrap ? V : 0;
+    img += wrap;
+  }
+  __device__ __forceinline__ bool live(int k) const { return first + 4 * k < S; }     // the wave's k-th slot exists
+};
+
+// The reference's bilinear resize (BmpImgIO::ReszImg, src/BmpImgIO.cc:105-178) of one value: pixel (Y, X) of channel ch of the
+// resized image from the four 8-bit taps of the h x w source at in + off, in the reference's fp32 sequence with one rounding per
+// operation (the build has -ffp-contract=off; the intrinsics say it again):
+//   yc = sy * (float)Y;  y0 = max(0, (int)yc);  y1 = min(h - 1, y0 + 1);  wy0 = 1 - (yc - (float)y0);  wy1 = 1 - ((float)y1 - yc)
+//   the columns likewise;  w00 = wy0 * wx0 ... w11 = wy1 * wx1
+//   (((p00 * w00 + p01 * w01) + p10 * w10) + p11 * w11) / (((w00 + w01) + w10) + w11)
+// yc is the float PRODUCT (for some sizes it lands just under or over an integer it equals mathematically: that moves y0 and
+// gives weights like 1 - eps or above 1), and the division is no no-op (y1 clamped to y0 at the last row: both row weights
+// about 1).  y0 is clamped to h - 1 as well: it cannot exceed it while h - 1 < 2^23, and beyond that the clamp keeps the taps
+// inside the image.  Offsets inside an image are 32-bit: C * h * w <= INT_MAX (the engine refuses images of 2 GiB and more).
+// bilinear_taps issues the four loads and waits for none (base and offset come apart: the image's 64-bit address is formed
+// behind the weights, next to the loads that use it); bilinear_value is the arithmetic on what they brought.
+struct BilinearTaps {
+  float w00, w01, w10, w11;
+  uint8_t p00, p01, p10, p11;
+};
+__device__ __forceinline__ void bilinear_taps(BilinearTaps& t, float sy, float sx, int h, int w, unsigned ch, int Y, int X,
+                                              const uint8_t* in, unsigned long long off) {
+  const float yc = __fmul_rn(sy, (float)Y), xc = __fmul_rn(sx, (float)X);
+  const int y0 = min(max(0, (int)yc), h - 1), x0 = min(max(0, (int)xc), w - 1);
+  const int y1 = min(h - 1, y0 + 1), x1 = min(w - 1, x0 + 1);
+  const float wy0 = __fsub_rn(1.0f, __fsub_rn(yc, (float)y0)), wy1 = __fsub_rn(1.0f, __fsub_rn((float)y1, yc));
+  const float wx0 = __fsub_rn(1.0f, __fsub_rn(xc, (float)x0)), wx1 = __fsub_rn(1.0f, __fsub_rn((float)x1, xc));
+  t.w00 = __fmul_rn(wy0, wx0); t.w01 = __fmul_rn(wy0, wx1); t.w10 = __fmul_rn(wy1, wx0); t.w11 = __fmul_rn(wy1, wx1);
+  const uint8_t* px = in + off;
+  const unsigned r0 = (ch * h + y0) * w, r1 = (ch * h + y1) * w;
+  t.p00 = px[r0 + x0]; t.p01 = px[r0 + x1]; t.p10 = px[r1 + x0]; t.p11 = px[r1 + x1];
+}
+__device__ __forceinline__ float bilinear_value(const BilinearTaps& t) {
+  const float num = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn((float)t.p00, t.w00), __fmul_rn((float)t.p01, t.w01)),
+                                        __fmul_rn((float)t.p10, t.w10)), __fmul_rn((float)t.p11, t.w11));
+  const float den = __fadd_rn(__fadd_rn(__fadd_rn(t.w00, t.w01), t.w10), t.w11);
+  return __fdiv_rn(num, den);
+}
+
+// [n][E] fp32 rows -> panels, rows kept (nchw = 0) or remapped NCHW -> NHWC.
 __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ in, float* __restrict__ dst, int n, int E,
                                               int C, int HW, int nchw) {
   __shared__ float tile[PANEL][65];
@@ -502,18 +580,14 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ in, floa
     for (int u = 0; u < 8; ++u) tile[wave + 4 * (b + u)][lane] = v[u];
   }
   __syncthreads();
-  for (int j = wave; j < 64; j += 4) {
-    const int e = e0 + j;
-    if (e < E) {
-      int row = e;
-      if (nchw) {
-        const int c = e / HW, hw = e % HW;
-        row = hw * C + c;
-      }
-      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + row) * PANEL + 2 * lane) =
-          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
+  tile_write_out(tile, dst, panel, e0, E, lane, wave, [=](int e) {
+    int row = e;
+    if (nchw) {
+      const int c = e / HW, hw = e % HW;
+      row = hw * C + c;
     }
-  }
+    return row;
+  });
 }
 
 // Device-side input pipeline: 8-bit planar images [n][C][Hs][Ws] (the B, G, R planes as
@@ -553,27 +627,19 @@ __global__ __launch_bounds__(256) void k_pack_u8(const uint8_t* __restrict__ in,
     }
   }
   __syncthreads();
-  for (int j = wave; j < 64; j += 4) {
-    const int ee = e0 + j;
-    if (ee < E) {
-      const int c = ee / HW, hw = ee % HW;
-      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)hw * C + c) * PANEL + 2 * lane) =
-          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
-    }
-  }
+  tile_write_out(tile, dst, panel, e0, E, lane, wave, NchwRow{C, HW});
 }
 
-// Multi-view form of k_pack_u8 (qcnn_forward_u8_views): S = n * V batch slots, slot s = view s % V of image s / V — the H x W
-// crop at (oy, ox) of that view, mirrored left-right where it says so.  Same 128-slot x 64-element LDS transpose, same
-// arithmetic (float(pixel) - mean, the mean taken at the SOURCE position: a mirrored view is the mirror of the plain one bit
-// for bit), but source offset and mean now belong to the (slot, element) pair.  The element part of the offset (channel
-// plane + row, column and mirrored column) is the thread's own and computed once; the slot part (image, oy * Ws + ox, flip) is
-// the same for all lanes of a wave: it comes from the kernel arguments through scalar loads, and image / view advance by the
-// wave's slot stride of four without a division per slot.  The loads are UNCONDITIONAL — a dead slot reads image 0, a dead
-// element reads element 0 of the view, both inside the source; what is dead is zeroed on its way into the tile — because a
-// load under a per-lane condition is compiled into a branch with a full wait behind it, one round trip per load; like this the
-// eight pixel and eight mean loads of a round are in flight together.  MEAN = false: no mean image.  Pixels of the ten views of
-// an image overlap: a source image is read from HBM once and from L2 after that; the panels written are what bounds the kernel.
+// Multi-view form of k_pack_u8 (qcnn_forward_u8_views): slot = the H x W crop at (oy, ox) of its view, mirrored left-right where
+// the view says so.  Same arithmetic (float(pixel) - mean, the mean taken at the SOURCE position: a mirrored view is the mirror
+// of the plain one bit for bit), but source offset and mean now belong to the (slot, element) pair.  The element part of the
+// offset (channel plane + row, column and mirrored column) is the thread's own and computed once; the slot part (image,
+// oy * Ws + ox, flip) is the wave's (SlotWalk), the views coming with the kernel arguments.  The loads are UNCONDITIONAL — a dead
+// slot reads image 0, a dead element reads element 0 of the view, both inside the source; what is dead is zeroed on its way into
+// the tile — because a load under a per-lane condition is compiled into a branch with a full wait behind it, one round trip per
+// load; like this the eight pixel and eight mean loads of a round are in flight together.  MEAN = false: no mean image.  Pixels
+// of the ten views of an image overlap: a source image is read from HBM once and from L2 after that; the panels written are
+// what bounds the kernel.
 template <bool MEAN>
 __global__ __launch_bounds__(256) void k_pack_u8_views(const uint8_t* __restrict__ in, const float* __restrict__ mean,
                                                        float* __restrict__ dst, int S, int V, const QkViews views, int C, int H,
@@ -588,60 +654,39 @@ __global__ __launch_bounds__(256) void k_pack_u8_views(const uint8_t* __restrict
   const unsigned rowOff = ((unsigned)(el / HW) * Hs + (el % HW) / W) * Ws;   // (c * Hs + y) * Ws: its row of the source at oy = 0
   const unsigned off0 = rowOff + el % W, off1 = rowOff + (W - 1 - el % W);   // ... + its column in a plain / a mirrored view
   const size_t srcImg = (size_t)C * Hs * Ws;        // < 2^31 (the launcher checks): offsets inside an image keep 32 bits
-  const int q4 = 4 / V, r4 = 4 % V;                 // the wave's next slot is four further: q4 images and r4 views
-  int img = (panel * PANEL + wave) / V, vw = (panel * PANEL + wave) % V;
+  SlotWalk s(panel, wave, V, S);
 #pragma unroll
   for (int b = 0; b < PANEL / 4; b += 8) {          // eight pixel (and eight mean) loads in flight per thread
     uint8_t v[8];
     float m[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const bool liveSlot = panel * PANEL + wave + 4 * (b + u) < S;     // wave-uniform
-      const QkView q = views.v[vw];                 // vw < V <= QK_MAX_VIEWS also for the dead slots of a ragged panel
+      const bool liveSlot = s.live(b + u);
+      const QkView q = views.v[s.vw];
       const unsigned soff = (q.flip ? off1 : off0) + (unsigned)(q.oy * Ws + q.ox);
-      v[u] = (in + (size_t)(liveSlot ? img : 0) * srcImg)[soff];
+      v[u] = (in + (size_t)(liveSlot ? s.img : 0) * srcImg)[soff];
       m[u] = MEAN ? mean[soff] : 0.0f;
-      img += q4;
-      vw += r4;
-      if (vw >= V) { vw -= V; ++img; }
+      s.next();
     }
     __builtin_amdgcn_sched_barrier(0);              // all sixteen loads are issued before the first value is waited for
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const bool live = panel * PANEL + wave + 4 * (b + u) < S && e < E;
+      const bool live = s.live(b + u) && e < E;
       tile[wave + 4 * (b + u)][lane] = live ? ((float)v[u] - m[u]) : 0.0f;
     }
     __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();
-  for (int j = wave; j < 64; j += 4) {
-    const int ee = e0 + j;
-    if (ee < E) {
-      const int c = ee / HW, hw = ee % HW;
-      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)hw * C + c) * PANEL + 2 * lane) =
-          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
-    }
-  }
+  tile_write_out(tile, dst, panel, e0, E, lane, wave, NchwRow{C, HW});
 }
 
-// k_pack_u8_views on source images of any size (qcnn_forward_u8_resized_views): slot s = view s % V of image s / V RESIZED to
-// Hf x Wf, the reference's BmpImgIO::ReszImg (Strict, src/BmpImgIO.cc:105-178) fused into the pack — the resized float images
-// are never stored (a thousand 256 x 256 x 3 float images are 786 MB; the panels written are already the HBM bound).  Every
-// (slot, element) computes its value from the four 8-bit taps of the slot's image with the reference's fp32 sequence, one
-// rounding per operation (the build has -ffp-contract=off; the intrinsics say it again):
-//   yc = sh * (float)Y;  y0 = max(0, (int)yc);  y1 = min(h - 1, y0 + 1);  wy0 = 1 - (yc - (float)y0);  wy1 = 1 - ((float)y1 - yc)
-//   the columns likewise;  w00 = wy0 * wx0 ... w11 = wy1 * wx1
-//   (((p00 * w00 + p01 * w01) + p10 * w10) + p11 * w11) / (((w00 + w01) + w10) + w11) - mean[c][Y][X]
-// with (Y, X) the element's position in the full image: view corner + (y, x or the mirrored x).  yc is the float PRODUCT (for
-// some sizes it lands just under or over an integer it equals mathematically: that moves y0 and gives weights like 1 - eps or
-// above 1), and the division is no no-op (y1 clamped to y0 at the last row: both row weights about 1).  y0 is clamped to h - 1
-// as well: it cannot exceed it while h - 1 < 2^23, and beyond that the clamp keeps the taps inside the image.
-// Same 128-slot x 64-element LDS transpose as k_pack_u8_views and what it learned: the loads are unconditional (a dead slot
-// reads image 0 with image 0's own descriptor, a dead element reads element 0; dead values are zeroed on the way into the tile),
-// so the four tap loads and the mean load of all slots of a round are in flight together; the slot part of the addressing — the
-// image's descriptor from the table the engine staged, the view from the kernel arguments — is wave-uniform and comes through
-// scalar loads; offsets inside an image are 32-bit (the engine refuses images of 2 GiB and more).  The two scales of an image
-// come with its descriptor (QkSrcImage).  Eight slots a round: forty loads in flight per thread.
+// k_pack_u8_views on source images of any size (qcnn_forward_u8_resized_views): each image RESIZED to Hf x Wf — ReszImg's Strict
+// mode, bilinear_taps with the two scales of the image's descriptor (QkSrcImage, from the table the engine staged) — fused into
+// the pack: the resized float images are never stored (a thousand 256 x 256 x 3 float images are 786 MB; the panels written
+// are already the HBM bound).  A (slot, element) is the resized value at (Y, X), the element's position in the full image —
+// view corner + (y, x or the mirrored x) — minus mean[c][Y][X].  Unconditional loads as in k_pack_u8_views (a dead slot reads
+// image 0 with image 0's own descriptor): the four tap loads and the mean load of the eight slots of a round, forty per
+// thread, are in flight together.
 template <bool MEAN>
 __global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restrict__ in, const QkSrcImage* __restrict__ desc,
                                                          const float* __restrict__ mean, float* __restrict__ dst, int S, int V,
@@ -655,73 +700,47 @@ __global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restri
   const int el = e < E ? e : 0;                     // the element whose source positions this thread reads
   const int ch = el / HW, ey = (el % HW) / W;       // its channel and its row in a view
   const int ex0 = el % W, ex1 = W - 1 - el % W;     // its column in a plain / a mirrored view
-  const int q4 = 4 / V, r4 = 4 % V;                 // the wave's next slot is four further: q4 images and r4 views
-  int img = (panel * PANEL + wave) / V, vw = (panel * PANEL + wave) % V;
+  SlotWalk s(panel, wave, V, S);
   constexpr int R = 8;                              // slots a round
 #pragma unroll
   for (int b = 0; b < PANEL / 4; b += R) {
-    uint8_t p00[R], p01[R], p10[R], p11[R];
-    float w00[R], w01[R], w10[R], w11[R], m[R];
+    BilinearTaps t[R];
+    float m[R];
 #pragma unroll
     for (int u = 0; u < R; ++u) {
-      const bool liveSlot = panel * PANEL + wave + 4 * (b + u) < S;     // wave-uniform
-      const QkSrcImage d = desc[liveSlot ? img : 0];
-      const QkView q = views.v[vw];                 // vw < V <= QK_MAX_VIEWS also for the dead slots of a ragged panel
+      const bool liveSlot = s.live(b + u);
+      const QkSrcImage d = desc[liveSlot ? s.img : 0];
+      const QkView q = views.v[s.vw];
       const int Y = q.oy + ey, X = q.ox + (q.flip ? ex1 : ex0);         // < Hf, < Wf: the engine checked the views
-      const float yc = __fmul_rn(d.sh, (float)Y), xc = __fmul_rn(d.sw, (float)X);
-      const int y0 = min(max(0, (int)yc), d.h - 1), x0 = min(max(0, (int)xc), d.w - 1);
-      const int y1 = min(d.h - 1, y0 + 1), x1 = min(d.w - 1, x0 + 1);
-      const float wy0 = __fsub_rn(1.0f, __fsub_rn(yc, (float)y0)), wy1 = __fsub_rn(1.0f, __fsub_rn((float)y1, yc));
-      const float wx0 = __fsub_rn(1.0f, __fsub_rn(xc, (float)x0)), wx1 = __fsub_rn(1.0f, __fsub_rn((float)x1, xc));
-      w00[u] = __fmul_rn(wy0, wx0); w01[u] = __fmul_rn(wy0, wx1); w10[u] = __fmul_rn(wy1, wx0); w11[u] = __fmul_rn(wy1, wx1);
-      const uint8_t* px = in + d.off;
-      const unsigned r0 = ((unsigned)ch * d.h + y0) * d.w, r1 = ((unsigned)ch * d.h + y1) * d.w;   // < C * h * w <= INT_MAX
-      p00[u] = px[r0 + x0]; p01[u] = px[r0 + x1]; p10[u] = px[r1 + x0]; p11[u] = px[r1 + x1];
+      bilinear_taps(t[u], d.sh, d.sw, d.h, d.w, ch, Y, X, in, d.off);
       m[u] = MEAN ? mean[((unsigned)ch * Hf + Y) * Wf + X] : 0.0f;
-      img += q4;
-      vw += r4;
-      if (vw >= V) { vw -= V; ++img; }
+      s.next();
     }
     __builtin_amdgcn_sched_barrier(0);              // every load of the round is issued before the first value is waited for
 #pragma unroll
     for (int u = 0; u < R; ++u) {
-      const bool live = panel * PANEL + wave + 4 * (b + u) < S && e < E;
-      const float num = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn((float)p00[u], w00[u]), __fmul_rn((float)p01[u], w01[u])),
-                                            __fmul_rn((float)p10[u], w10[u])), __fmul_rn((float)p11[u], w11[u]));
-      const float den = __fadd_rn(__fadd_rn(__fadd_rn(w00[u], w01[u]), w10[u]), w11[u]);
-      const float val = __fdiv_rn(num, den);
+      const bool live = s.live(b + u) && e < E;
+      const float val = bilinear_value(t[u]);
       tile[wave + 4 * (b + u)][lane] = live ? (MEAN ? __fsub_rn(val, m[u]) : val) : 0.0f;
     }
     __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();
-  for (int j = wave; j < 64; j += 4) {
-    const int ee = e0 + j;
-    if (ee < E) {
-      const int c = ee / HW, hw = ee % HW;
-      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)hw * C + c) * PANEL + 2 * lane) =
-          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
-    }
-  }
+  tile_write_out(tile, dst, panel, e0, E, lane, wave, NchwRow{C, HW});
 }
 
 // k_pack_u8_resized for the reference's other pre-processing mode (qcnn_forward_u8_relaxed_views): BmpImgIO::ReszImg Relaxed —
 // ONE scale s for both axes, so image i has its own full size hf x wf (both computed by the engine on the host with the
 // reference's float sequence and staged with the descriptor, QkRelaxedImage) — then CropImg and a mean of the CROP's size
-// (ENUM_MeanType::Crop, src/BmpImgIO.cc:56-64,124-131).  Per (slot, element) the value is the resized kernel's with sh = sw = s:
-//   (((p00 * w00 + p01 * w01) + p10 * w10) + p11 * w11) / (((w00 + w01) + w10) + w11) - mean[c][y][xl]
-// at the full-image position (Y, X) = (oy + y, ox + xl), xl = x or the mirrored column, and what differs is where the slot
-// part comes from:
+// (ENUM_MeanType::Crop, src/BmpImgIO.cc:56-64,124-131).  A (slot, element) is the resized value at the full-image position
+// (Y, X) = (oy + y, ox + xl), xl = x or the mirrored column, minus mean[c][y][xl]; against the resized kernel:
 //   * the view corner is resolved per slot from the view's anchor and ITS image's full size, wave-uniformly, in scalar
 //     registers: o = (((full - in) * a) >> 1) + d, which is 0, CropImg's (full - in) / 2 and full - in for a = 0, 1, 2 (full >= in:
 //     the engine checked every view against every image);
 //   * the mean is indexed by the element alone (view-local position BEFORE mirroring), so its loads leave the slot loop: two
 //     per thread per block — the plain and the mirrored column, a slot picks by its wave-uniform flip — where the resized
-//     kernel issues one per slot.
-// Everything else is k_pack_u8_resized: the 128-slot x 64-element LDS transpose, unconditional loads (a dead slot reads image 0
-// under its view, which the engine checked like every other pair; taps are clamped into the image besides), eight slots a
-// round with their 32 tap loads in flight before the first is waited for, descriptor and view through scalar loads, 32-bit
-// offsets inside an image, one rounding per operation.
+//     kernel issues one per slot: 32 tap loads a round.
+// A dead slot reads image 0 under its view, which the engine checked like every other pair.
 template <bool MEAN>
 __global__ __launch_bounds__(256) void k_pack_u8_relaxed(const uint8_t* __restrict__ in, const QkRelaxedImage* __restrict__ desc,
                                                          const float* __restrict__ mean, float* __restrict__ dst, int S, int V,
@@ -738,56 +757,34 @@ __global__ __launch_bounds__(256) void k_pack_u8_relaxed(const uint8_t* __restri
   const unsigned ch = el / HW;                      // its channel
   const float mPlain = MEAN ? mean[el] : 0.0f;      // mean[c][ey][ex0]: el = (c * H + ey) * W + ex0
   const float mFlip = MEAN ? mean[el - ex0 + ex1] : 0.0f;
-  const int q4 = 4 / V, r4 = 4 % V;                 // the wave's next slot is four further: q4 images and r4 views
-  int img = (panel * PANEL + wave) / V, vw = (panel * PANEL + wave) % V;
+  SlotWalk s(panel, wave, V, S);
   constexpr int R = 8;                              // slots a round
 #pragma unroll
   for (int b = 0; b < PANEL / 4; b += R) {
-    uint8_t p00[R], p01[R], p10[R], p11[R];
-    float w00[R], w01[R], w10[R], w11[R];
+    BilinearTaps t[R];
     bool flip[R];
 #pragma unroll
     for (int u = 0; u < R; ++u) {
-      const bool liveSlot = panel * PANEL + wave + 4 * (b + u) < S;     // wave-uniform
-      const QkRelaxedImage d = desc[liveSlot ? img : 0];
-      const QkAnchorView q = views.v[vw];           // vw < V <= QK_MAX_VIEWS also for the dead slots of a ragged panel
+      const bool liveSlot = s.live(b + u);
+      const QkRelaxedImage d = desc[liveSlot ? s.img : 0];
+      const QkAnchorView q = views.v[s.vw];
       const int oy = (((d.hf - H) * q.ay) >> 1) + q.dy, ox = (((d.wf - W) * q.ax) >> 1) + q.dx;
       flip[u] = q.flip != 0;
       const int Y = oy + ey, X = ox + (flip[u] ? ex1 : ex0);            // < hf, < wf: the engine checked view x image
-      const float yc = __fmul_rn(d.s, (float)Y), xc = __fmul_rn(d.s, (float)X);
-      const int y0 = min(max(0, (int)yc), d.h - 1), x0 = min(max(0, (int)xc), d.w - 1);
-      const int y1 = min(d.h - 1, y0 + 1), x1 = min(d.w - 1, x0 + 1);
-      const float wy0 = __fsub_rn(1.0f, __fsub_rn(yc, (float)y0)), wy1 = __fsub_rn(1.0f, __fsub_rn((float)y1, yc));
-      const float wx0 = __fsub_rn(1.0f, __fsub_rn(xc, (float)x0)), wx1 = __fsub_rn(1.0f, __fsub_rn((float)x1, xc));
-      w00[u] = __fmul_rn(wy0, wx0); w01[u] = __fmul_rn(wy0, wx1); w10[u] = __fmul_rn(wy1, wx0); w11[u] = __fmul_rn(wy1, wx1);
-      const uint8_t* px = in + d.off;
-      const unsigned r0 = (ch * d.h + y0) * d.w, r1 = (ch * d.h + y1) * d.w;   // < C * h * w <= INT_MAX
-      p00[u] = px[r0 + x0]; p01[u] = px[r0 + x1]; p10[u] = px[r1 + x0]; p11[u] = px[r1 + x1];
-      img += q4;
-      vw += r4;
-      if (vw >= V) { vw -= V; ++img; }
+      bilinear_taps(t[u], d.s, d.s, d.h, d.w, ch, Y, X, in, d.off);
+      s.next();
     }
     __builtin_amdgcn_sched_barrier(0);              // every load of the round is issued before the first value is waited for
 #pragma unroll
     for (int u = 0; u < R; ++u) {
-      const bool live = panel * PANEL + wave + 4 * (b + u) < S && e < E;
-      const float num = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn((float)p00[u], w00[u]), __fmul_rn((float)p01[u], w01[u])),
-                                            __fmul_rn((float)p10[u], w10[u])), __fmul_rn((float)p11[u], w11[u]));
-      const float den = __fadd_rn(__fadd_rn(__fadd_rn(w00[u], w01[u]), w10[u]), w11[u]);
-      const float val = __fdiv_rn(num, den);
+      const bool live = s.live(b + u) && e < E;
+      const float val = bilinear_value(t[u]);
       tile[wave + 4 * (b + u)][lane] = live ? (MEAN ? __fsub_rn(val, flip[u] ? mFlip : mPlain) : val) : 0.0f;
     }
     __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();
-  for (int j = wave; j < 64; j += 4) {
-    const int ee = e0 + j;
-    if (ee < E) {
-      const int c = ee / HW, hw = ee % HW;
-      *reinterpret_cast<f32x2*>(dst + ((size_t)panel * E + (size_t)hw * C + c) * PANEL + 2 * lane) =
-          f32x2{tile[2 * lane][j], tile[2 * lane + 1][j]};
-    }
-  }
+  tile_write_out(tile, dst, panel, e0, E, lane, wave, NchwRow{C, HW});
 }
 
 // Class probabilities of n * V slots -> their mean over the V views of each of n images, both in panels [C][128]: one thread =

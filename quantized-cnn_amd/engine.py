@@ -25,11 +25,29 @@ DEFAULT_EC_RIDGE = 1e-6   # its ridge, in units of the mean diagonal of the gram
 EC_GRAM_RUN = 256         # QCNN_EC_GRAM_RUN: patches calib_gram sums in fp32 before the sums move to fp64
 
 
+def _ptr(p):
+    """An address as the C-ABI takes it: NULL for None (and 0)."""
+    return C.c_void_p(p) if p else None
+
+
+def _struct_array(ctype, rows):
+    """(ctypes array, length) of a sequence of rows of ints — views (oy, ox, flip) / (ay, ax, dy, dx, flip), descriptors
+    (offset, h, w); an empty sequence still gives an array the C side may be handed."""
+    rs = [tuple(int(x) for x in r) for r in rows]
+    return (ctype * max(len(rs), 1))(*[ctype(*r) for r in rs]), len(rs)
+
+
+def _desc_array(descs):
+    if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcImage:     # made once by the caller: no per-call conversion
+        return descs, len(descs)
+    return _struct_array(capi.QcnnSrcImage, descs)
+
+
 class QcnnEngine:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load()
         h = C.c_void_p()
-        rc = self.lib.qcnn_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(h))
+        rc = self.lib.qcnn_ctx_create(device, _ptr(stream), C.byref(h))
         if rc:
             raise QcnnError(self.lib.qcnn_last_error(None).decode())
         self.h = h
@@ -74,7 +92,7 @@ class QcnnEngine:
         return n.value
 
     def commit(self, max_batch: int, arena_ptr: int | None = None):
-        self._chk(self.lib.qcnn_model_commit(self.h, max_batch, C.c_void_p(arena_ptr) if arena_ptr else None))
+        self._chk(self.lib.qcnn_model_commit(self.h, max_batch, _ptr(arena_ptr)))
         self.max_batch = max_batch
 
     def upload(self, params):
@@ -224,18 +242,13 @@ class QcnnEngine:
     # -- forward --------------------------------------------------------------------------------
     def forward_dev(self, in_ptr: int, n: int, prob_ptr: int | None = None, top5_ptr: int | None = None):
         """Asynchronous, device pointers (e.g. torch tensors' data_ptr())."""
-        self._chk(self.lib.qcnn_forward(self.h, C.c_void_p(in_ptr), n,
-                                        C.c_void_p(prob_ptr) if prob_ptr else None,
-                                        C.c_void_p(top5_ptr) if top5_ptr else None))
+        self._chk(self.lib.qcnn_forward(self.h, _ptr(in_ptr), n, _ptr(prob_ptr), _ptr(top5_ptr)))
 
     def forward_u8_dev(self, in_ptr: int, src_h: int, src_w: int, mean_ptr: int | None, n: int,
                        prob_ptr: int | None = None, top5_ptr: int | None = None):
         """Asynchronous, device pointers: 8-bit planar images [n][C][src_h][src_w], mean [C][src_h][src_w] or None;
         mean subtraction + centre crop happen on the device (BmpImgIO::RmMeanImg/CropImg)."""
-        self._chk(self.lib.qcnn_forward_u8(self.h, C.c_void_p(in_ptr), src_h, src_w,
-                                           C.c_void_p(mean_ptr) if mean_ptr else None, n,
-                                           C.c_void_p(prob_ptr) if prob_ptr else None,
-                                           C.c_void_p(top5_ptr) if top5_ptr else None))
+        self._chk(self.lib.qcnn_forward_u8(self.h, _ptr(in_ptr), src_h, src_w, _ptr(mean_ptr), n, _ptr(prob_ptr), _ptr(top5_ptr)))
 
     def forward_u8_views_dev(self, in_ptr: int, src_h: int, src_w: int, mean_ptr: int | None, n: int, views,
                              prob_ptr: int | None = None, top5_ptr: int | None = None, prob_views_ptr: int | None = None):
@@ -244,13 +257,9 @@ class QcnnEngine:
         flip: mirrored left-right (ten_crop_views gives the standard ten).  Batch slot i * len(views) + v is view v of image i;
         prob [n][classes] / top5 [n][5] are those of the probabilities averaged over an image's views, prob_views
         [n][len(views)][classes] the un-averaged rows."""
-        vs = [tuple(int(x) for x in v) for v in views]
-        arr = (capi.QcnnView * max(len(vs), 1))(*[capi.QcnnView(*v) for v in vs])
-        self._chk(self.lib.qcnn_forward_u8_views(self.h, C.c_void_p(in_ptr), src_h, src_w,
-                                                 C.c_void_p(mean_ptr) if mean_ptr else None, n, arr, len(vs),
-                                                 C.c_void_p(prob_ptr) if prob_ptr else None,
-                                                 C.c_void_p(top5_ptr) if top5_ptr else None,
-                                                 C.c_void_p(prob_views_ptr) if prob_views_ptr else None))
+        varr, V = _struct_array(capi.QcnnView, views)
+        self._chk(self.lib.qcnn_forward_u8_views(self.h, _ptr(in_ptr), src_h, src_w, _ptr(mean_ptr), n, varr, V,
+                                                 _ptr(prob_ptr), _ptr(top5_ptr), _ptr(prob_views_ptr)))
 
     def forward_u8_resized_views_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int, mean_ptr: int | None,
                                      views, prob_ptr: int | None = None, top5_ptr: int | None = None,
@@ -260,47 +269,22 @@ class QcnnEngine:
         views).  descs: a sequence of (offset, h, w) — image i is [C][h][w] at src_ptr + offset (pack_sources makes buffer and
         list); mean [C][full_h][full_w] or None; views as forward_u8_views_dev takes them, cut from the full image.  Neither
         list has to outlive the call."""
-        if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcImage:     # made once by the caller: no per-call conversion
-            darr, n = descs, len(descs)
-        else:
-            ds = [tuple(int(x) for x in d) for d in descs]
-            darr, n = (capi.QcnnSrcImage * max(len(ds), 1))(*[capi.QcnnSrcImage(*d) for d in ds]), len(ds)
-        vs = [tuple(int(x) for x in v) for v in views]
-        varr = (capi.QcnnView * max(len(vs), 1))(*[capi.QcnnView(*v) for v in vs])
-        self._chk(self.lib.qcnn_forward_u8_resized_views(self.h, C.c_void_p(src_ptr), src_bytes, darr, n, full_h, full_w,
-                                                         C.c_void_p(mean_ptr) if mean_ptr else None, varr, len(vs),
-                                                         C.c_void_p(prob_ptr) if prob_ptr else None,
-                                                         C.c_void_p(top5_ptr) if top5_ptr else None,
-                                                         C.c_void_p(prob_views_ptr) if prob_views_ptr else None))
+        darr, n = _desc_array(descs)
+        varr, V = _struct_array(capi.QcnnView, views)
+        self._chk(self.lib.qcnn_forward_u8_resized_views(self.h, _ptr(src_ptr), src_bytes, darr, n, full_h, full_w, _ptr(mean_ptr),
+                                                         varr, V, _ptr(prob_ptr), _ptr(top5_ptr), _ptr(prob_views_ptr)))
 
     def forward_u8_resized_host(self, images, full_hw, mean=None, views=None):
         """Blocking convenience: images — a list of uint8 arrays [C][h][w] of differing sizes — are packed, uploaded, resized
         to full_hw = (full_h, full_w) on the device, the float32 mean [C][full_h][full_w] (or None) subtracted, and evaluated on
         `views` (default: the centre crop alone, which makes the call BmpImgIO::Load + the forward pass).  Returns (prob
         [n][classes] averaged over the views, top5 [n][5], prob_views [n][len(views)][classes]) as numpy arrays."""
-        import torch   # plumbing only: device buffers and copies
         full_h, full_w = int(full_hw[0]), int(full_hw[1])
         _, in_h, in_w = self.in_chw
         if views is None:
             views = [((full_h - in_h) // 2, (full_w - in_w) // 2, 0)]
-        flat, descs = pack_sources(images)
-        n, V = len(descs), len(views)
-        fh, fw, fc = self.fm_dims(self.L)
-        classes = fh * fw * fc
-        dev = torch.device("cuda", self.lib.qcnn_ctx_device(self.h))
-        d_src = torch.from_numpy(flat).to(dev)
-        d_mean = torch.from_numpy(np.ascontiguousarray(mean, np.float32)).to(dev) if mean is not None else None
-        if d_mean is not None and tuple(d_mean.shape) != (self.in_chw[0], full_h, full_w):
-            raise QcnnError("mean image %r, expected %r" % (tuple(d_mean.shape), (self.in_chw[0], full_h, full_w)))
-        d_prob = torch.empty((n, classes), dtype=torch.float32, device=dev)
-        d_top5 = torch.empty((n, 5), dtype=torch.int16, device=dev)
-        d_rows = torch.empty((n, max(V, 1), classes), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        self.forward_u8_resized_views_dev(d_src.data_ptr(), flat.size, descs, full_h, full_w,
-                                          d_mean.data_ptr() if d_mean is not None else None, views,
-                                          d_prob.data_ptr(), d_top5.data_ptr(), d_rows.data_ptr())
-        self.sync()
-        return d_prob.cpu().numpy(), d_top5.cpu().numpy().view(np.uint16), d_rows.cpu().numpy()
+        return self._u8_host(self.forward_u8_resized_views_dev, images, full_h, full_w, mean, "mean image",
+                             (self.in_chw[0], full_h, full_w), views)
 
     def forward_u8_relaxed_views_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int, mean_crop_ptr: int | None,
                                      views, prob_ptr: int | None = None, top5_ptr: int | None = None,
@@ -311,18 +295,11 @@ class QcnnEngine:
         forward_u8_resized_views_dev takes them; mean_crop [C][in_h][in_w] or None; views: a sequence of (ay, ax, dy, dx, flip)
         (ten_crop_anchored gives the standard ten; (1, 1, 0, 0, 0) is BmpImgIO's centre crop).  Neither list has to outlive
         the call."""
-        if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcImage:     # made once by the caller: no per-call conversion
-            darr, n = descs, len(descs)
-        else:
-            ds = [tuple(int(x) for x in d) for d in descs]
-            darr, n = (capi.QcnnSrcImage * max(len(ds), 1))(*[capi.QcnnSrcImage(*d) for d in ds]), len(ds)
-        vs = [tuple(int(x) for x in v) for v in views]
-        varr = (capi.QcnnAnchorView * max(len(vs), 1))(*[capi.QcnnAnchorView(*v) for v in vs])
-        self._chk(self.lib.qcnn_forward_u8_relaxed_views(self.h, C.c_void_p(src_ptr), src_bytes, darr, n, full_h, full_w,
-                                                         C.c_void_p(mean_crop_ptr) if mean_crop_ptr else None, varr, len(vs),
-                                                         C.c_void_p(prob_ptr) if prob_ptr else None,
-                                                         C.c_void_p(top5_ptr) if top5_ptr else None,
-                                                         C.c_void_p(prob_views_ptr) if prob_views_ptr else None))
+        darr, n = _desc_array(descs)
+        varr, V = _struct_array(capi.QcnnAnchorView, views)
+        self._chk(self.lib.qcnn_forward_u8_relaxed_views(self.h, _ptr(src_ptr), src_bytes, darr, n, full_h, full_w,
+                                                         _ptr(mean_crop_ptr), varr, V, _ptr(prob_ptr), _ptr(top5_ptr),
+                                                         _ptr(prob_views_ptr)))
 
     def forward_u8_relaxed_host(self, images, full_hw, mean_crop=None, views=None):
         """Blocking convenience: images — a list of uint8 arrays [C][h][w] of differing sizes — are packed, uploaded, resized
@@ -330,26 +307,29 @@ class QcnnEngine:
         None) subtracted, and evaluated on `views` (default: the centre anchor alone, which makes the call BmpImgIO::Load of a
         Relaxed / Crop model + the forward pass).  Returns (prob [n][classes] averaged over the views, top5 [n][5], prob_views
         [n][len(views)][classes]) as numpy arrays."""
-        import torch   # plumbing only: device buffers and copies
-        full_h, full_w = int(full_hw[0]), int(full_hw[1])
         if views is None:
             views = [(1, 1, 0, 0, 0)]
+        return self._u8_host(self.forward_u8_relaxed_views_dev, images, int(full_hw[0]), int(full_hw[1]), mean_crop, "crop mean",
+                             tuple(self.in_chw), views)
+
+    def _u8_host(self, call, images, full_h, full_w, mean, mean_name, mean_shape, views):
+        """The blocking 8-bit calls around their asynchronous one: pack and upload, `call`, wait, download."""
+        import torch   # plumbing only: device buffers and copies
         flat, descs = pack_sources(images)
         n, V = len(descs), len(views)
         fh, fw, fc = self.fm_dims(self.L)
         classes = fh * fw * fc
         dev = torch.device("cuda", self.lib.qcnn_ctx_device(self.h))
         d_src = torch.from_numpy(flat).to(dev)
-        d_mean = torch.from_numpy(np.ascontiguousarray(mean_crop, np.float32)).to(dev) if mean_crop is not None else None
-        if d_mean is not None and tuple(d_mean.shape) != tuple(self.in_chw):
-            raise QcnnError("crop mean %r, expected %r" % (tuple(d_mean.shape), tuple(self.in_chw)))
+        d_mean = torch.from_numpy(np.ascontiguousarray(mean, np.float32)).to(dev) if mean is not None else None
+        if d_mean is not None and tuple(d_mean.shape) != mean_shape:
+            raise QcnnError("%s %r, expected %r" % (mean_name, tuple(d_mean.shape), mean_shape))
         d_prob = torch.empty((n, classes), dtype=torch.float32, device=dev)
         d_top5 = torch.empty((n, 5), dtype=torch.int16, device=dev)
         d_rows = torch.empty((n, max(V, 1), classes), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)
-        self.forward_u8_relaxed_views_dev(d_src.data_ptr(), flat.size, descs, full_h, full_w,
-                                          d_mean.data_ptr() if d_mean is not None else None, views,
-                                          d_prob.data_ptr(), d_top5.data_ptr(), d_rows.data_ptr())
+        call(d_src.data_ptr(), flat.size, descs, full_h, full_w, d_mean.data_ptr() if d_mean is not None else None, views,
+             d_prob.data_ptr(), d_top5.data_ptr(), d_rows.data_ptr())
         self.sync()
         return d_prob.cpu().numpy(), d_top5.cpu().numpy().view(np.uint16), d_rows.cpu().numpy()
 

@@ -10,6 +10,7 @@ tests/test_resize_cpu.py holds to the compiled reference — and tests/views_ref
   * the whole path on the tiny network against qcnn_forward_host of the host-made inputs at the same slot count; three slots on
     the few-image kernels; NULL outputs; the descriptor staging grows; calls back to back without a sync between them;
   * every rejected argument: non-zero with a message, outputs and fm[0] untouched, the next call right."""
+import functools
 import itertools
 
 import numpy as np
@@ -20,73 +21,17 @@ import glue_ref as gr
 import resize_ref as rr
 import views_ref as vr
 from conftest import pkg, tiny_params_from_golden
+from u8_harness import DEV, Outputs, Source, bits_equal, make_engine, run_sources
 
 pytestmark = pytest.mark.gpu
 
 topo = pkg("topology")
 capi = pkg("capi")
 engine = pkg("engine")
-DEV = torch.device("cuda", 0)
 
 
-def make_engine(in_chw, layers, params, max_batch, lut=None):
-    eng = engine.QcnnEngine(0)
-    eng.set_option(capi.OPT_KEEP_ALL, 1)          # fm[0] stays readable
-    if lut is not None:
-        eng.set_option(capi.OPT_LUT_MODE, lut)
-    eng.load_model(in_chw, layers, params, max_batch)
-    return eng
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-class Outputs:
-    """Device outputs of one call, pre-filled with NaN / -1: what a call leaves untouched shows."""
-
-    def __init__(self, eng, n, V, want=(True, True, True)):
-        h, w, c = eng.fm_dims(eng.L)
-        self.classes = h * w * c
-        self.prob = torch.full((max(n, 1), self.classes), float("nan"), dtype=torch.float32, device=DEV) if want[0] else None
-        self.top5 = torch.full((max(n, 1), 5), -1, dtype=torch.int16, device=DEV) if want[1] else None
-        self.rows = torch.full((max(n * V, 1), self.classes), float("nan"), dtype=torch.float32, device=DEV) if want[2] else None
-
-    def ptrs(self):
-        return tuple(t.data_ptr() if t is not None else None for t in (self.prob, self.top5, self.rows))
-
-    def host(self):
-        return (self.prob.cpu().numpy() if self.prob is not None else None,
-                self.top5.cpu().numpy().view(np.uint16) if self.top5 is not None else None,
-                self.rows.cpu().numpy() if self.rows is not None else None)
-
-    def untouched(self):
-        p, t, r = self.host()
-        return ((p is None or np.isnan(p).all()) and (t is None or (t == 0xFFFF).all()) and (r is None or np.isnan(r).all()))
-
-
-class Source:
-    """Images of differing sizes packed into one device buffer (engine.pack_sources) + the mean on the device."""
-
-    def __init__(self, images, mean):
-        self.flat, self.descs = engine.pack_sources(images)
-        self.d_flat = torch.from_numpy(self.flat).to(DEV)
-        self.d_mean = torch.from_numpy(mean).to(DEV) if mean is not None else None
-        torch.cuda.synchronize()
-
-    def call(self, eng, full, views, out, descs=None, src_bytes=None):
-        eng.forward_u8_resized_views_dev(self.d_flat.data_ptr(), self.flat.size if src_bytes is None else src_bytes,
-                                         self.descs if descs is None else descs, full[0], full[1],
-                                         self.d_mean.data_ptr() if self.d_mean is not None else None, views, *out.ptrs())
-
-
-def run_resized(eng, images, full, mean, views, want=(True, True, True)):
-    src = Source(images, mean)
-    out = Outputs(eng, len(images), len(views), want)
-    src.call(eng, full, views, out)
-    eng.sync()
-    return out.host()
+Source = functools.partial(Source, "forward_u8_resized_views_dev")
+run_resized = functools.partial(run_sources, "forward_u8_resized_views_dev")
 
 
 # ---------------------------------------------------------------------------------------------- 1. the pack kernel, per element

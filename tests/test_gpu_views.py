@@ -14,47 +14,26 @@ import torch
 import glue_ref as gr
 import views_ref as vr
 from conftest import pkg, tiny_params_from_golden
+from u8_harness import DEV, Outputs, bits_equal, make_engine
 
 pytestmark = pytest.mark.gpu
 
 topo = pkg("topology")
 capi = pkg("capi")
 engine = pkg("engine")
-DEV = torch.device("cuda", 0)
-
-
-def make_engine(in_chw, layers, params, max_batch, lut=None):
-    eng = engine.QcnnEngine(0)
-    eng.set_option(capi.OPT_KEEP_ALL, 1)          # fm[0] stays readable; the 8-bit path packs, so does qcnn_forward here
-    if lut is not None:
-        eng.set_option(capi.OPT_LUT_MODE, lut)
-    eng.load_model(in_chw, layers, params, max_batch)
-    return eng
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def run_views(eng, px, mean, views, want_prob=True, want_top5=True, want_rows=True):
     """qcnn_forward_u8_views on device copies of px / mean -> (prob [n][classes], top5 [n][5], rows [n*V][classes]); None where
-    the output was not asked for.  Outputs start as NaN / -1: what the call leaves untouched shows."""
-    n, V = px.shape[0], len(views)
-    h, w, c = eng.fm_dims(eng.L)
-    classes = h * w * c
+    the output was not asked for."""
     d_px = torch.from_numpy(px).to(DEV)
     d_mean = torch.from_numpy(mean).to(DEV) if mean is not None else None
-    d_prob = torch.full((n, classes), float("nan"), dtype=torch.float32, device=DEV) if want_prob else None
-    d_top5 = torch.full((n, 5), -1, dtype=torch.int16, device=DEV) if want_top5 else None
-    d_rows = torch.full((max(n * V, 1), classes), float("nan"), dtype=torch.float32, device=DEV) if want_rows else None
+    out = Outputs(eng, px.shape[0], len(views), (want_prob, want_top5, want_rows))
     torch.cuda.synchronize()
-    eng.forward_u8_views_dev(d_px.data_ptr(), px.shape[2], px.shape[3], d_mean.data_ptr() if mean is not None else None, n, views,
-                             d_prob.data_ptr() if want_prob else None, d_top5.data_ptr() if want_top5 else None,
-                             d_rows.data_ptr() if want_rows else None)
+    eng.forward_u8_views_dev(d_px.data_ptr(), px.shape[2], px.shape[3], d_mean.data_ptr() if mean is not None else None,
+                             px.shape[0], views, *out.ptrs())
     eng.sync()
-    return (d_prob.cpu().numpy() if want_prob else None, d_top5.cpu().numpy().view(np.uint16) if want_top5 else None,
-            d_rows.cpu().numpy() if want_rows else None)
+    return out.host()
 
 
 # ---------------------------------------------------------------------------------------------- 1. the pack kernel, per element
