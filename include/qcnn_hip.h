@@ -30,6 +30,9 @@
  *   / qcnn_views_ten_crop       probabilities averaged on the device
  *   qcnn_forward_u8_resized_views  BmpImgIO::ReszImg (Strict) in front of them, sources of any size  src/BmpImgIO.cc:105-178
  *   qcnn_forward_u8_relaxed_views  ReszImg (Relaxed) + CropImg + a crop-sized mean (VggCnnS) in front  src/BmpImgIO.cc:56-64,124-131
+ *   qcnn_src_bmp + qcnn_forward_u8_resized_views_strided / _relaxed_views_strided
+ *                               BmpImgIO::LoadBmpImg: the de-interleave, the flip and the row re-packing  src/BmpImgIO.cc:73-103
+ *                               (the file's pixel array is read where it lies; so is a decoder's HWC output or a region of a frame)
  *   qcnn_model_set_layer_dense  CaffePara::LoadLayerPara(false, ..) result src/CaffePara.cc:290-302
  *   / _set_layer_weights        -> CalcFeatMap_ConvPrec / _FCntPrec        src/CaffeEva.cc:681-758, 932-966
  *   qcnn_quantize_layer         produces what CaffePara::LoadLayerPara reads src/CaffePara.cc:262-288
@@ -392,6 +395,57 @@ int qcnn_forward_u8_relaxed_views(QcnnCtx* ctx, const uint8_t* src_dev, size_t s
                                   int full_h, int full_w, const float* mean_crop_dev /* [C][in_h][in_w] or NULL */,
                                   const QcnnAnchorView* views_host, int n_views,
                                   float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
+/* Source images read IN PLACE, whatever their layout: interleaved (a decoder's HWC output, a BMP file's pixel array), pitched
+ * (a camera frame, a rectangle inside a larger one), bottom-up (BMP), planar with gaps.  An image is described by strides:
+ * sample (c, y, x) of image i — c in the network's channel order B, G, R; (0, 0) the TOP-LEFT pixel as the network sees it — is
+ * the byte at
+ *   src_dev + offset + y * row_stride + x * pix_stride + ch_offset[c]
+ * The planar layout of QcnnSrcImage is row_stride = w, pix_stride = 1, ch_offset[c] = c * h * w (qcnn_src_planar); a bottom-up
+ * BMP has offset at its LAST file row and a negative row_stride (qcnn_src_bmp).  Samples may alias (a grey image fed to three
+ * channels: all ch_offset equal; row_stride 0; two descriptors naming overlapping regions of one frame): the source is only
+ * read.  Bytes that are no sample (padding, alpha, gaps, the frame around a region, file headers) are never read. */
+typedef struct {
+  uint64_t offset;       /* byte, relative to src_dev, of pixel (0, 0): the TOP-LEFT pixel of the image as the network sees it */
+  int64_t  row_stride;   /* bytes from pixel (y, x) to (y + 1, x); negative = rows stored bottom-up */
+  int32_t  h, w;
+  int32_t  pix_stride;   /* bytes from pixel (y, x) to (y, x + 1); >= 1 */
+  int32_t  ch_offset[4]; /* byte of network channel c (c < C, network order B, G, R) relative to its pixel; >= 0; entries c >= C ignored */
+} QcnnSrcPixels;         /* 48 bytes with the trailing padding */
+/* The descriptor of a planar image (host only: no device, no context).  Non-zero, nothing written: img or out NULL, C outside
+ * [1, 4], h < 1 or w < 1, C * h * w > INT32_MAX. */
+int qcnn_src_planar(const QcnnSrcImage* img, int C, QcnnSrcPixels* out);
+/* The descriptor of the pixel array of a BMP file whose bytes will lie at src_dev + file_offset — the whole file, header
+ * included, is uploaded untouched (host only: file_host is read here, no device, no context).  Accepted are exactly the flavours
+ * the host mirror's BmpImgIO decodes: the BM signature, a file of at least 54 bytes, 24 or 32 bits per pixel, compression 0,
+ * a positive width, a height of either sign (negative = top-down; 0 and INT32_MIN are refused), rows padded to 4 bytes, the file
+ * at least dataOff + stride * h bytes long.  Every other file: non-zero, nothing written (so is a NULL pointer or a
+ * file_offset + file_bytes beyond 64 bits).  h = |height|, pix_stride = 3 or 4, ch_offset = {0, 1, 2, 0} (the file order is B, G,
+ * R); bottom-up: offset = file_offset + dataOff + (h - 1) * stride, row_stride = -stride; top-down: offset = file_offset +
+ * dataOff, row_stride = stride. */
+int qcnn_src_bmp(const uint8_t* file_host, size_t file_bytes, uint64_t file_offset, QcnnSrcPixels* out);
+/* qcnn_forward_u8_resized_views / qcnn_forward_u8_relaxed_views on such images.  Everything but the place of a tap's byte is
+ * defined there: scales, taps, weights, the division, the mean's position, mirroring, slot order, averaging, top-5, the three
+ * optional outputs, the staging of the host arrays, asynchrony.  Given the planar descriptors the calls return the planar
+ * calls' bits; a source of the full size through the resized call returns qcnn_forward_u8_views' bits under every layout.
+ * Checked before anything is enqueued (non-zero, a message naming the image, outputs untouched): everything the planar call
+ * checks — h, w >= 1 (Strict) or >= 2 (Relaxed) — and, in overflow-checked 64-bit arithmetic (a row_stride of INT64_MIN or an
+ * offset near 2^64 is refused, not wrapped):
+ *   a network of more than 4 input channels;  pix_stride < 1;  ch_offset[c] < 0 for a c < C;
+ *   lowest byte touched   offset + min(0, (h-1) * row_stride)                                            below 0;
+ *   highest byte touched  offset + max(0, (h-1) * row_stride) + (w-1) * pix_stride + max_c ch_offset[c]  >= src_bytes
+ *                         (a layout whose last sample is byte src_bytes - 1 is accepted);
+ *   highest - lowest >= 2^31 - 1  (the kernels keep offsets relative to `offset` in signed 32 bits).
+ * row_stride is otherwise free: 0 and values smaller than a row are legal if in bounds. */
+int qcnn_forward_u8_resized_views_strided(QcnnCtx* ctx, const uint8_t* src_dev, size_t src_bytes,
+                                          const QcnnSrcPixels* imgs_host, int n, int full_h, int full_w,
+                                          const float* mean_dev /* [C][full_h][full_w] or NULL */,
+                                          const QcnnView* views_host, int n_views,
+                                          float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
+int qcnn_forward_u8_relaxed_views_strided(QcnnCtx* ctx, const uint8_t* src_dev, size_t src_bytes,
+                                          const QcnnSrcPixels* imgs_host, int n, int full_h, int full_w,
+                                          const float* mean_crop_dev /* [C][in_h][in_w] or NULL */,
+                                          const QcnnAnchorView* views_host, int n_views,
+                                          float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
 /* Blocking convenience: host in, host out (H2D + forward + D2H + sync).  A batch of at least two chunks
  * (QCNN_OPT_HOST_CHUNK) goes through chunk by chunk, uploads overlapped with the previous chunk's layers. */
 int qcnn_forward_host(QcnnCtx* ctx, const float* in_nchw_host, int n, float* prob_host, uint16_t* top5_host);

@@ -36,6 +36,13 @@ class QcnnSrcImage(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class QcnnSrcPixels(C.Structure):
+    """A source image of the strided calls, read in place: sample (c, y, x) is the byte at offset + y * row_stride +
+    x * pix_stride + ch_offset[c] of the source buffer ((0, 0): the top-left pixel; c in the network's order B, G, R)."""
+    _fields_ = [("offset", C.c_uint64), ("row_stride", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("pix_stride", C.c_int32), ("ch_offset", C.c_int32 * 4)]
+
+
 class QcnnAnchorView(C.Structure):
     """A view of qcnn_forward_u8_relaxed_views, placed relative to each image's own full size: anchor 0 / 1 / 2 = near edge /
     CropImg's centre / far edge on each axis, plus dy / dx pixels; flip: mirrored left-right."""
@@ -98,6 +105,12 @@ def load():
     lib.qcnn_relaxed_full_size.argtypes = [i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_float)]
     lib.qcnn_forward_u8_relaxed_views.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcImage), i, i, i, f32p, C.POINTER(QcnnAnchorView), i,
                                                   f32p, u16p, f32p]
+    lib.qcnn_src_planar.argtypes = [C.POINTER(QcnnSrcImage), i, C.POINTER(QcnnSrcPixels)]
+    lib.qcnn_src_bmp.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.POINTER(QcnnSrcPixels)]
+    lib.qcnn_forward_u8_resized_views_strided.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcPixels), i, i, i, f32p,
+                                                          C.POINTER(QcnnView), i, f32p, u16p, f32p]
+    lib.qcnn_forward_u8_relaxed_views_strided.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcPixels), i, i, i, f32p,
+                                                          C.POINTER(QcnnAnchorView), i, f32p, u16p, f32p]
     lib.qcnn_forward_host.argtypes = [vp, f32p, i, f32p, u16p]
     lib.qcnn_forward_host_batches.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp)]
     lib.qcnn_host_register.argtypes = [vp, C.c_size_t]

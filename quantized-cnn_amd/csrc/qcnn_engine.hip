@@ -22,6 +22,7 @@
 #include "../../include/qcnn_hip.h"
 #include "qcnn_kernels.h"
 #include "qcnn_planner.h"
+#include "qcnn_src_layout.h"
 
 namespace {
 
@@ -1816,6 +1817,16 @@ int src_image_ok(QcnnCtx* c, int i, const QcnnSrcImage& s, size_t src_bytes, int
     return fail(c, "image %d: %llu bytes at offset %llu leave the source buffer of %zu bytes", i, bytes, (unsigned long long)s.offset, src_bytes);
   return 0;
 }
+// Source image i of a strided call: the same for a layout given by strides (qcnn_src_layout.h holds the rules).
+int src_pixels_ok(QcnnCtx* c, int i, const QcnnSrcPixels& s, size_t src_bytes, int minSide) {
+  char why[256];
+  if (qcnn_src::check_pixels(s, c->inC, src_bytes, minSide, why, sizeof(why))) return fail(c, "image %d: %s", i, why);
+  return 0;
+}
+// The layout of a checked descriptor as the kernels take it: row_stride's low 32 bits (they differ from it only where h == 1).
+QkLayout layout_of(const QcnnSrcPixels& s) {
+  return QkLayout{(int)(uint32_t)(uint64_t)s.row_stride, s.pix_stride, s.ch_offset[0], s.ch_offset[1], s.ch_offset[2], s.ch_offset[3]};
+}
 // Stage n descriptors D — fill(i) makes image i's — and launch the pack kernel that reads them.  Called when every argument
 // is good: nothing is taken or rewritten for a call that is refused.  The set is marked in flight only once nothing of the
 // host's can fail any more, and its event is recorded behind its one reader.
@@ -1846,27 +1857,71 @@ int qcnn_forward_u8_views(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int s
   return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
-int qcnn_forward_u8_resized_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
-                                  int full_h, int full_w, const float* mean_dev, const QcnnView* views_host, int n_views,
-                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  if (views_open(c, "qcnn_forward_u8_resized_views", src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views",
-                 n, n_views) || full_image_ok(c, full_h, full_w))
+namespace {
+// What the planar and the strided calls differ in, by the type of the caller's descriptor: its check, the image part of the
+// staged descriptor, the staged descriptor itself and the pack launch.
+extern "C++" {                                      // overloads
+int src_ok(QcnnCtx* c, int i, const QcnnSrcImage& s, size_t src_bytes, int minSide) { return src_image_ok(c, i, s, src_bytes, minSide); }
+int src_ok(QcnnCtx* c, int i, const QcnnSrcPixels& s, size_t src_bytes, int minSide) { return src_pixels_ok(c, i, s, src_bytes, minSide); }
+QkSrcImage staged(const QcnnSrcImage&, const QkSrcImage& img) { return img; }
+QkSrcPixels staged(const QcnnSrcPixels& s, const QkSrcImage& img) { return QkSrcPixels{img, layout_of(s)}; }
+QkRelaxedImage staged(const QcnnSrcImage&, const QkRelaxedImage& img) { return img; }
+QkRelaxedPixels staged(const QcnnSrcPixels& s, const QkRelaxedImage& img) { return QkRelaxedPixels{img, layout_of(s)}; }
+hipError_t pack_resized(const uint8_t* in, const QkSrcImage* d, const float* mean, float* dst, int n, int V, const QkViews& views, int C,
+                        int H, int W, int Hf, int Wf, hipStream_t st) { return qk_pack_u8_resized(in, d, mean, dst, n, V, views, C, H, W, Hf, Wf, st); }
+hipError_t pack_resized(const uint8_t* in, const QkSrcPixels* d, const float* mean, float* dst, int n, int V, const QkViews& views, int C,
+                        int H, int W, int Hf, int Wf, hipStream_t st) { return qk_pack_u8_resized_strided(in, d, mean, dst, n, V, views, C, H, W, Hf, Wf, st); }
+hipError_t pack_relaxed(const uint8_t* in, const QkRelaxedImage* d, const float* mean, float* dst, int n, int V, const QkAnchorViews& views,
+                        int C, int H, int W, hipStream_t st) { return qk_pack_u8_relaxed(in, d, mean, dst, n, V, views, C, H, W, st); }
+hipError_t pack_relaxed(const uint8_t* in, const QkRelaxedPixels* d, const float* mean, float* dst, int n, int V, const QkAnchorViews& views,
+                        int C, int H, int W, hipStream_t st) { return qk_pack_u8_relaxed_strided(in, d, mean, dst, n, V, views, C, H, W, st); }
+}  // extern "C++"
+
+// qcnn_forward_u8_resized_views (Src = QcnnSrcImage) and qcnn_forward_u8_resized_views_strided (Src = QcnnSrcPixels).
+extern "C++" template <class Src>
+int resized_views(QcnnCtx* c, const char* fn, const uint8_t* src_dev, size_t src_bytes, const Src* imgs_host, int n, int full_h,
+                  int full_w, const float* mean_dev, const QcnnView* views_host, int n_views, float* prob_dev, uint16_t* top5_dev,
+                  float* prob_views_dev) {
+  if (views_open(c, fn, src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views", n, n_views) ||
+      full_image_ok(c, full_h, full_w))
     return 1;
   QkViews views = {};
   if (crop_views(c, views_host, n_views, full_h, full_w, "full", &views)) return 1;
   for (int i = 0; i < n; ++i)
-    if (src_image_ok(c, i, imgs_host[i], src_bytes, 1)) return 1;
-  if (stage_and_pack<QkSrcImage>(
+    if (src_ok(c, i, imgs_host[i], src_bytes, 1)) return 1;
+  using D = decltype(staged(imgs_host[0], QkSrcImage{}));
+  if (stage_and_pack<D>(
           c, n, prob_dev || top5_dev,
           [&](int i) {                                // the scales: one IEEE division each, as ReszImg computes them
-            const QcnnSrcImage& s = imgs_host[i];
-            return QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)};
+            const Src& s = imgs_host[i];
+            return staged(s, QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)});
           },
-          [&](const QkSrcImage* desc) {
-            return qk_pack_u8_resized(src_dev, desc, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
+          [&](const D* desc) {
+            return pack_resized(src_dev, desc, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
           }))
     return 1;
   return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
+}
+}  // namespace
+
+int qcnn_forward_u8_resized_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
+                                  int full_h, int full_w, const float* mean_dev, const QcnnView* views_host, int n_views,
+                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  return resized_views(c, "qcnn_forward_u8_resized_views", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host, n_views,
+                       prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_forward_u8_resized_views_strided(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcPixels* imgs_host, int n,
+                                          int full_h, int full_w, const float* mean_dev, const QcnnView* views_host, int n_views,
+                                          float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  return resized_views(c, "qcnn_forward_u8_resized_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host,
+                       n_views, prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_src_planar(const QcnnSrcImage* img, int C, QcnnSrcPixels* out) { return qcnn_src::planar_pixels(img, C, out); }
+
+int qcnn_src_bmp(const uint8_t* file_host, size_t file_bytes, uint64_t file_offset, QcnnSrcPixels* out) {
+  return qcnn_src::bmp_pixels(file_host, file_bytes, file_offset, out);
 }
 
 int qcnn_views_ten_crop_anchored(QcnnAnchorView* views10) {
@@ -1890,11 +1945,14 @@ int qcnn_relaxed_full_size(int h, int w, int full_h, int full_w, int* hf, int* w
   return 0;
 }
 
-int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
-                                  int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
-                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  if (views_open(c, "qcnn_forward_u8_relaxed_views", src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views",
-                 n, n_views) || full_image_ok(c, full_h, full_w))
+namespace {
+// qcnn_forward_u8_relaxed_views (Src = QcnnSrcImage) and qcnn_forward_u8_relaxed_views_strided (Src = QcnnSrcPixels).
+extern "C++" template <class Src>
+int relaxed_views(QcnnCtx* c, const char* fn, const uint8_t* src_dev, size_t src_bytes, const Src* imgs_host, int n, int full_h,
+                  int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views, float* prob_dev,
+                  uint16_t* top5_dev, float* prob_views_dev) {
+  if (views_open(c, fn, src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views", n, n_views) ||
+      full_image_ok(c, full_h, full_w))
     return 1;
   QkAnchorViews views = {};
   for (int v = 0; v < n_views; ++v) {
@@ -1903,8 +1961,8 @@ int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src
     views.v[v] = QkAnchorView{q.ay, q.ax, q.dy, q.dx, q.flip ? 1 : 0};
   }
   for (int i = 0; i < n; ++i) {
-    const QcnnSrcImage& s = imgs_host[i];
-    if (src_image_ok(c, i, s, src_bytes, 2)) return 1;
+    const Src& s = imgs_host[i];
+    if (src_ok(c, i, s, src_bytes, 2)) return 1;
     int hf = 0, wf = 0;
     if (qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &hf, &wf, nullptr))
       return fail(c, "image %d: %dx%d resized towards %dx%d has a side of 2^24 pixels or more", i, s.h, s.w, full_h, full_w);
@@ -1916,19 +1974,35 @@ int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src
                     c->inW, oy, ox, hf, wf, s.h, s.w);
     }
   }
-  if (stage_and_pack<QkRelaxedImage>(
+  using D = decltype(staged(imgs_host[0], QkRelaxedImage{}));
+  if (stage_and_pack<D>(
           c, n, prob_dev || top5_dev,
           [&](int i) {                                // each image's scale and full size
-            const QcnnSrcImage& s = imgs_host[i];
+            const Src& s = imgs_host[i];
             QkRelaxedImage d = {s.offset, s.h, s.w, 0.0f, 0, 0, 0};
             (void)qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &d.hf, &d.wf, &d.s);     // succeeded above
-            return d;
+            return staged(s, d);
           },
-          [&](const QkRelaxedImage* desc) {
-            return qk_pack_u8_relaxed(src_dev, desc, mean_crop_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, c->stream);
+          [&](const D* desc) {
+            return pack_relaxed(src_dev, desc, mean_crop_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, c->stream);
           }))
     return 1;
   return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
+}
+}  // namespace
+
+int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
+                                  int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
+                                  float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  return relaxed_views(c, "qcnn_forward_u8_relaxed_views", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev, views_host,
+                       n_views, prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_forward_u8_relaxed_views_strided(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcPixels* imgs_host, int n,
+                                          int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host,
+                                          int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  return relaxed_views(c, "qcnn_forward_u8_relaxed_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev,
+                       views_host, n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
 int qcnn_host_register(void* ptr, size_t bytes) {

@@ -3,7 +3,8 @@
 // the FC layers' split partial sums, and the conversions between the reference's NCHW / row-major host layouts and the
 // 128-image panels (:1146-1160, :187-189), among them the 8-bit input pipelines (one centre crop per image, or several crops and
 // mirrors per image with the mean of their class probabilities: k_pack_u8_views, k_mean_views; the same from source images of any
-// size, resized on the way: k_pack_u8_resized, k_pack_u8_relaxed).  All of them are streaming kernels bound by HBM (or, for LRN, by the
+// size, resized on the way: k_pack_u8_resized, k_pack_u8_relaxed — each also for images read in place under any layout given by
+// strides: their instantiations on QkSrcPixels / QkRelaxedPixels).  All of them are streaming kernels bound by HBM (or, for LRN, by the
 // expf/logf pair); the two hot kernels live in qcnn_kernels.hip.  Feature maps are panels [pixel][channel][128 images]
 // (qcnn_kernels.h); a float4 lane carries four images.
 #include "qcnn_kernels.h"
@@ -541,17 +542,67 @@ struct BilinearTaps {
   float w00, w01, w10, w11;
   uint8_t p00, p01, p10, p11;
 };
-__device__ __forceinline__ void bilinear_taps(BilinearTaps& t, float sy, float sx, int h, int w, unsigned ch, int Y, int X,
-                                              const uint8_t* in, unsigned long long off) {
+// WHERE the four taps lie is the layout's (tap_loads): planar [C][h][w] for QkSrcImage / QkRelaxedImage, the strides of a
+// QkLayout for the strided descriptors.  Either way the image's part — base, sizes, strides, channel offsets — is wave-uniform
+// and scalar, the thread's part a 32-bit offset, and the loads are unconditional.
+__device__ __forceinline__ void tap_loads(BilinearTaps& t, const uint8_t* px, int h, int w, unsigned ch, int y0, int y1, int x0,
+                                          int x1) {
+  const unsigned r0 = (ch * h + y0) * w, r1 = (ch * h + y1) * w;
+  t.p00 = px[r0 + x0]; t.p01 = px[r0 + x1]; t.p10 = px[r1 + x0]; t.p11 = px[r1 + x1];
+}
+// QK_STRIDED_VAR (LABBOOK.md, "Source layouts"; timing only, results wrong but for planar descriptors under bit 2): 1 = the
+// strided kernels without the channel select, 2 = with the planar address arithmetic on their 48- / 56-byte descriptors.
+#ifndef QK_STRIDED_VAR
+#define QK_STRIDED_VAR 0
+#endif
+// Strided: y * rs + x * ps + co[ch] modulo 2^32, read as an int (qcnn_kernels.h, QkLayout: the true sum is one).  ch is the
+// thread's own: it picks among the four uniform channel offsets by selects.
+__device__ __forceinline__ void tap_loads(BilinearTaps& t, const uint8_t* px, const QkLayout& l, unsigned ch, int y0, int y1,
+                                          int x0, int x1) {
+  // The four fields are read first, unconditionally, and each select picks between two VALUES: a conditional whose arms read
+  // the fields becomes one read at a selected address, and the descriptor is then copied to scratch to be indexed there.
+  const unsigned a0 = l.c0, a1 = l.c1, a2 = l.c2, a3 = l.c3;
+  unsigned co = a3;
+  co = ch == 2 ? a2 : co;
+  co = ch == 1 ? a1 : co;
+  co = ch == 0 ? a0 : co;
+#if QK_STRIDED_VAR & 1
+  co = a0;                                          // timing only: no channel select
+#endif
+  const unsigned r0 = (unsigned)y0 * (unsigned)l.rs + co, r1 = (unsigned)y1 * (unsigned)l.rs + co;
+  const unsigned c0 = (unsigned)x0 * (unsigned)l.ps, c1 = (unsigned)x1 * (unsigned)l.ps;
+  t.p00 = px[(int)(r0 + c0)]; t.p01 = px[(int)(r0 + c1)]; t.p10 = px[(int)(r1 + c0)]; t.p11 = px[(int)(r1 + c1)];
+}
+// What a pack kernel asks of its descriptor type D: the image part (offset, sizes, scales) and the taps' loads.
+__device__ __forceinline__ const QkSrcImage& image_of(const QkSrcImage& d) { return d; }
+__device__ __forceinline__ const QkSrcImage& image_of(const QkSrcPixels& d) { return d.img; }
+__device__ __forceinline__ const QkRelaxedImage& image_of(const QkRelaxedImage& d) { return d; }
+__device__ __forceinline__ const QkRelaxedImage& image_of(const QkRelaxedPixels& d) { return d.img; }
+__device__ __forceinline__ void tap_loads(BilinearTaps& t, const uint8_t* px, const QkSrcImage& d, unsigned ch, int y0, int y1,
+                                          int x0, int x1) { tap_loads(t, px, d.h, d.w, ch, y0, y1, x0, x1); }
+__device__ __forceinline__ void tap_loads(BilinearTaps& t, const uint8_t* px, const QkRelaxedImage& d, unsigned ch, int y0, int y1,
+                                          int x0, int x1) { tap_loads(t, px, d.h, d.w, ch, y0, y1, x0, x1); }
+#if QK_STRIDED_VAR & 2
+#define QK_STRIDED_TAPS(d) tap_loads(t, px, d.img.h, d.img.w, ch, y0, y1, x0, x1)
+#else
+#define QK_STRIDED_TAPS(d) tap_loads(t, px, d.lay, ch, y0, y1, x0, x1)
+#endif
+__device__ __forceinline__ void tap_loads(BilinearTaps& t, const uint8_t* px, const QkSrcPixels& d, unsigned ch, int y0, int y1,
+                                          int x0, int x1) { QK_STRIDED_TAPS(d); }
+__device__ __forceinline__ void tap_loads(BilinearTaps& t, const uint8_t* px, const QkRelaxedPixels& d, unsigned ch, int y0, int y1,
+                                          int x0, int x1) { QK_STRIDED_TAPS(d); }
+template <class D>
+__device__ __forceinline__ void bilinear_taps(BilinearTaps& t, float sy, float sx, const D& d, unsigned ch, int Y, int X,
+                                              const uint8_t* in) {
+  const int h = image_of(d).h, w = image_of(d).w;
   const float yc = __fmul_rn(sy, (float)Y), xc = __fmul_rn(sx, (float)X);
   const int y0 = min(max(0, (int)yc), h - 1), x0 = min(max(0, (int)xc), w - 1);
   const int y1 = min(h - 1, y0 + 1), x1 = min(w - 1, x0 + 1);
   const float wy0 = __fsub_rn(1.0f, __fsub_rn(yc, (float)y0)), wy1 = __fsub_rn(1.0f, __fsub_rn((float)y1, yc));
   const float wx0 = __fsub_rn(1.0f, __fsub_rn(xc, (float)x0)), wx1 = __fsub_rn(1.0f, __fsub_rn((float)x1, xc));
   t.w00 = __fmul_rn(wy0, wx0); t.w01 = __fmul_rn(wy0, wx1); t.w10 = __fmul_rn(wy1, wx0); t.w11 = __fmul_rn(wy1, wx1);
-  const uint8_t* px = in + off;
-  const unsigned r0 = (ch * h + y0) * w, r1 = (ch * h + y1) * w;
-  t.p00 = px[r0 + x0]; t.p01 = px[r0 + x1]; t.p10 = px[r1 + x0]; t.p11 = px[r1 + x1];
+  const uint8_t* px = in + image_of(d).off;
+  tap_loads(t, px, d, ch, y0, y1, x0, x1);
 }
 __device__ __forceinline__ float bilinear_value(const BilinearTaps& t) {
   const float num = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn((float)t.p00, t.w00), __fmul_rn((float)t.p01, t.w01)),
@@ -687,8 +738,8 @@ __global__ __launch_bounds__(256) void k_pack_u8_views(const uint8_t* __restrict
 // view corner + (y, x or the mirrored x) — minus mean[c][Y][X].  Unconditional loads as in k_pack_u8_views (a dead slot reads
 // image 0 with image 0's own descriptor): the four tap loads and the mean load of the eight slots of a round, forty per
 // thread, are in flight together.
-template <bool MEAN>
-__global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restrict__ in, const QkSrcImage* __restrict__ desc,
+template <bool MEAN, class D>                         // D: QkSrcImage (planar) or QkSrcPixels (strided)
+__global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restrict__ in, const D* __restrict__ desc,
                                                          const float* __restrict__ mean, float* __restrict__ dst, int S, int V,
                                                          const QkViews views, int C, int H, int W, int Hf, int Wf) {
   __shared__ float tile[PANEL][65];
@@ -709,10 +760,10 @@ __global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restri
 #pragma unroll
     for (int u = 0; u < R; ++u) {
       const bool liveSlot = s.live(b + u);
-      const QkSrcImage d = desc[liveSlot ? s.img : 0];
+      const D d = desc[liveSlot ? s.img : 0];
       const QkView q = views.v[s.vw];
       const int Y = q.oy + ey, X = q.ox + (q.flip ? ex1 : ex0);         // < Hf, < Wf: the engine checked the views
-      bilinear_taps(t[u], d.sh, d.sw, d.h, d.w, ch, Y, X, in, d.off);
+      bilinear_taps(t[u], image_of(d).sh, image_of(d).sw, d, ch, Y, X, in);
       m[u] = MEAN ? mean[((unsigned)ch * Hf + Y) * Wf + X] : 0.0f;
       s.next();
     }
@@ -741,8 +792,8 @@ __global__ __launch_bounds__(256) void k_pack_u8_resized(const uint8_t* __restri
 //     per thread per block — the plain and the mirrored column, a slot picks by its wave-uniform flip — where the resized
 //     kernel issues one per slot: 32 tap loads a round.
 // A dead slot reads image 0 under its view, which the engine checked like every other pair.
-template <bool MEAN>
-__global__ __launch_bounds__(256) void k_pack_u8_relaxed(const uint8_t* __restrict__ in, const QkRelaxedImage* __restrict__ desc,
+template <bool MEAN, class D>                         // D: QkRelaxedImage (planar) or QkRelaxedPixels (strided)
+__global__ __launch_bounds__(256) void k_pack_u8_relaxed(const uint8_t* __restrict__ in, const D* __restrict__ desc,
                                                          const float* __restrict__ mean, float* __restrict__ dst, int S, int V,
                                                          const QkAnchorViews views, int C, int H, int W) {
   __shared__ float tile[PANEL][65];
@@ -766,12 +817,12 @@ __global__ __launch_bounds__(256) void k_pack_u8_relaxed(const uint8_t* __restri
 #pragma unroll
     for (int u = 0; u < R; ++u) {
       const bool liveSlot = s.live(b + u);
-      const QkRelaxedImage d = desc[liveSlot ? s.img : 0];
+      const D d = desc[liveSlot ? s.img : 0];
       const QkAnchorView q = views.v[s.vw];
-      const int oy = (((d.hf - H) * q.ay) >> 1) + q.dy, ox = (((d.wf - W) * q.ax) >> 1) + q.dx;
+      const int oy = (((image_of(d).hf - H) * q.ay) >> 1) + q.dy, ox = (((image_of(d).wf - W) * q.ax) >> 1) + q.dx;
       flip[u] = q.flip != 0;
       const int Y = oy + ey, X = ox + (flip[u] ? ex1 : ex0);            // < hf, < wf: the engine checked view x image
-      bilinear_taps(t[u], d.s, d.s, d.h, d.w, ch, Y, X, in, d.off);
+      bilinear_taps(t[u], image_of(d).s, image_of(d).s, d, ch, Y, X, in);
       s.next();
     }
     __builtin_amdgcn_sched_barrier(0);              // every load of the round is issued before the first value is waited for
@@ -977,27 +1028,53 @@ hipError_t qk_pack_u8_views(const uint8_t* in, const float* mean, float* dst, in
   return hipGetLastError();
 }
 
-hipError_t qk_pack_u8_resized(const uint8_t* in, const QkSrcImage* desc, const float* mean, float* dst, int n, int V,
-                              const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st) {
+namespace {
+// The launchers of the two resizing pack kernels, for the planar and the strided descriptor type alike.
+template <class D>
+hipError_t launch_pack_resized(const uint8_t* in, const D* desc, const float* mean, float* dst, int n, int V, const QkViews& views,
+                               int C, int H, int W, int Hf, int Wf, hipStream_t st) {
   if (n <= 0 || V < 1 || V > QK_MAX_VIEWS || !in || !desc || Hf < 2 || Wf < 2) return hipErrorInvalidValue;
   for (int v = 0; v < V; ++v)                       // a view outside the full image must never reach the kernel
     if (views.v[v].oy < 0 || views.v[v].ox < 0 || views.v[v].oy > Hf - H || views.v[v].ox > Wf - W) return hipErrorInvalidValue;
   if ((long long)C * Hf * Wf > INT_MAX) return hipErrorInvalidValue;   // the mean's offsets are 32-bit too
   const int E = C * H * W, S = n * V;
-  hipLaunchKernelGGL(mean ? k_pack_u8_resized<true> : k_pack_u8_resized<false>, dim3((E + 63) / 64, panels_of(S)), dim3(256), 0,
-                     st, in, desc, mean, dst, S, V, views, C, H, W, Hf, Wf);
+  hipLaunchKernelGGL(mean ? HIP_KERNEL_NAME(k_pack_u8_resized<true, D>) : HIP_KERNEL_NAME(k_pack_u8_resized<false, D>),
+                     dim3((E + 63) / 64, panels_of(S)), dim3(256), 0, st, in, desc, mean, dst, S, V, views, C, H, W, Hf, Wf);
   return hipGetLastError();
 }
-
-hipError_t qk_pack_u8_relaxed(const uint8_t* in, const QkRelaxedImage* desc, const float* mean, float* dst, int n, int V,
-                              const QkAnchorViews& views, int C, int H, int W, hipStream_t st) {
+template <class D>
+hipError_t launch_pack_relaxed(const uint8_t* in, const D* desc, const float* mean, float* dst, int n, int V,
+                               const QkAnchorViews& views, int C, int H, int W, hipStream_t st) {
   if (n <= 0 || V < 1 || V > QK_MAX_VIEWS || !in || !desc || C < 1 || H < 1 || W < 1) return hipErrorInvalidValue;
   for (int v = 0; v < V; ++v)                       // an anchor outside 0..2 must never reach the kernel
     if (views.v[v].ay < 0 || views.v[v].ay > 2 || views.v[v].ax < 0 || views.v[v].ax > 2) return hipErrorInvalidValue;
   const int E = C * H * W, S = n * V;
-  hipLaunchKernelGGL(mean ? k_pack_u8_relaxed<true> : k_pack_u8_relaxed<false>, dim3((E + 63) / 64, panels_of(S)), dim3(256), 0,
-                     st, in, desc, mean, dst, S, V, views, C, H, W);
+  hipLaunchKernelGGL(mean ? HIP_KERNEL_NAME(k_pack_u8_relaxed<true, D>) : HIP_KERNEL_NAME(k_pack_u8_relaxed<false, D>),
+                     dim3((E + 63) / 64, panels_of(S)), dim3(256), 0, st, in, desc, mean, dst, S, V, views, C, H, W);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t qk_pack_u8_resized(const uint8_t* in, const QkSrcImage* desc, const float* mean, float* dst, int n, int V,
+                              const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st) {
+  return launch_pack_resized(in, desc, mean, dst, n, V, views, C, H, W, Hf, Wf, st);
+}
+
+hipError_t qk_pack_u8_relaxed(const uint8_t* in, const QkRelaxedImage* desc, const float* mean, float* dst, int n, int V,
+                              const QkAnchorViews& views, int C, int H, int W, hipStream_t st) {
+  return launch_pack_relaxed(in, desc, mean, dst, n, V, views, C, H, W, st);
+}
+
+hipError_t qk_pack_u8_resized_strided(const uint8_t* in, const QkSrcPixels* desc, const float* mean, float* dst, int n, int V,
+                                      const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st) {
+  if (C > 4) return hipErrorInvalidValue;           // a QkLayout names four channels
+  return launch_pack_resized(in, desc, mean, dst, n, V, views, C, H, W, Hf, Wf, st);
+}
+
+hipError_t qk_pack_u8_relaxed_strided(const uint8_t* in, const QkRelaxedPixels* desc, const float* mean, float* dst, int n, int V,
+                                      const QkAnchorViews& views, int C, int H, int W, hipStream_t st) {
+  if (C > 4) return hipErrorInvalidValue;
+  return launch_pack_relaxed(in, desc, mean, dst, n, V, views, C, H, W, st);
 }
 
 hipError_t qk_mean_views(const float* src, float* dst, int n, int V, int C, hipStream_t st) {

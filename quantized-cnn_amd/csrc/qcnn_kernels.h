@@ -461,6 +461,19 @@ struct QkAnchorViews { QkAnchorView v[QK_MAX_VIEWS]; };
 // memory; the caller checked every descriptor against the source buffer and every view against every image's hf x wf.
 hipError_t qk_pack_u8_relaxed(const uint8_t* in, const QkRelaxedImage* desc, const float* mean, float* dst, int n, int V,
                               const QkAnchorViews& views, int C, int H, int W, hipStream_t st);
+// The strided forms (qcnn_forward_u8_resized_views_strided / _relaxed_views_strided): the same descriptors with the layout of a
+// QcnnSrcPixels behind them — sample (c, y, x) is the byte at in + off + (int)(y * rs + x * ps + co[c]), the sum formed in 32 bits
+// (modulo 2^32 it is exact: the engine checked that every sample lies less than 2^31 - 1 bytes from every other, so the true
+// sum is an int; rs is row_stride's low 32 bits, which differ from it only where h == 1 and the product is 0).  Types of their
+// own beside QkSrcImage / QkRelaxedImage, which keep their size and the planar kernels their code.
+struct QkLayout { int rs, ps, c0, c1, c2, c3; };          // c0 .. c3: ch_offset[0 .. 3], named (an array invites an indexed read)
+struct QkSrcPixels { QkSrcImage img; QkLayout lay; };               // 48 bytes
+struct QkRelaxedPixels { QkRelaxedImage img; QkLayout lay; };       // 56 bytes
+// qk_pack_u8_resized / qk_pack_u8_relaxed on such descriptors (C <= 4); everything else as there.
+hipError_t qk_pack_u8_resized_strided(const uint8_t* in, const QkSrcPixels* desc, const float* mean, float* dst, int n, int V,
+                                      const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st);
+hipError_t qk_pack_u8_relaxed_strided(const uint8_t* in, const QkRelaxedPixels* desc, const float* mean, float* dst, int n, int V,
+                                      const QkAnchorViews& views, int C, int H, int W, hipStream_t st);
 // panels [C][128] of n * V slots -> panels [C][128] of n images: the mean over the V slots of an image, summed in slot order
 // in fp32 and divided by (float)V (lanes >= n zero-filled)
 hipError_t qk_mean_views(const float* src, float* dst, int n, int V, int C, hipStream_t st);

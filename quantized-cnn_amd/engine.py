@@ -7,6 +7,7 @@ pointers.  The C++ host mirror (include/CaffeEva.h of this repo) is the same thi
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -41,6 +42,35 @@ def _desc_array(descs):
     if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcImage:     # made once by the caller: no per-call conversion
         return descs, len(descs)
     return _struct_array(capi.QcnnSrcImage, descs)
+
+
+class SrcPixels(collections.namedtuple("SrcPixels", "offset row_stride h w pix_stride ch_offset")):
+    """A source image of the strided calls as Python holds it (capi.QcnnSrcPixels): sample (c, y, x) is the byte at offset +
+    y * row_stride + x * pix_stride + ch_offset[c] of the source buffer.  ch_offset: up to four ints, network order B, G, R."""
+    __slots__ = ()
+
+    def sample_index(self, C):
+        """int64 [C][h][w]: the byte of every sample in the source buffer (numpy indexing reads the image through it)."""
+        c = np.asarray(self.ch_offset[:C], np.int64)[:, None, None]
+        y = np.arange(self.h, dtype=np.int64)[None, :, None]
+        x = np.arange(self.w, dtype=np.int64)[None, None, :]
+        return int(self.offset) + y * int(self.row_stride) + x * int(self.pix_stride) + c
+
+
+def _pixels_array(descs):
+    """(ctypes array of QcnnSrcPixels, length) of SrcPixels / (offset, row_stride, h, w, pix_stride, ch_offset) rows."""
+    if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcPixels:    # made once by the caller: no per-call conversion
+        return descs, len(descs)
+    rows = list(descs)
+    arr = (capi.QcnnSrcPixels * max(len(rows), 1))()
+    for d, (off, rs, h, w, ps, co) in zip(arr, rows):
+        co = tuple(int(v) for v in co) + (0,) * (4 - len(co))
+        d.offset, d.row_stride, d.h, d.w, d.pix_stride, d.ch_offset = int(off), int(rs), int(h), int(w), int(ps), (C.c_int32 * 4)(*co)
+    return arr, len(rows)
+
+
+def _from_c(d):
+    return SrcPixels(int(d.offset), int(d.row_stride), int(d.h), int(d.w), int(d.pix_stride), tuple(int(v) for v in d.ch_offset))
 
 
 class QcnnEngine:
@@ -274,17 +304,31 @@ class QcnnEngine:
         self._chk(self.lib.qcnn_forward_u8_resized_views(self.h, _ptr(src_ptr), src_bytes, darr, n, full_h, full_w, _ptr(mean_ptr),
                                                          varr, V, _ptr(prob_ptr), _ptr(top5_ptr), _ptr(prob_views_ptr)))
 
-    def forward_u8_resized_host(self, images, full_hw, mean=None, views=None):
+    def forward_u8_resized_views_strided_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int,
+                                             mean_ptr: int | None, views, prob_ptr: int | None = None,
+                                             top5_ptr: int | None = None, prob_views_ptr: int | None = None):
+        """forward_u8_resized_views_dev on source images read in place, whatever their layout
+        (qcnn_forward_u8_resized_views_strided).  descs: a sequence of SrcPixels — src_planar, src_bmp, pack_bmp_files and
+        pack_interleaved make them — or a ready ctypes array of capi.QcnnSrcPixels."""
+        darr, n = _pixels_array(descs)
+        varr, V = _struct_array(capi.QcnnView, views)
+        self._chk(self.lib.qcnn_forward_u8_resized_views_strided(self.h, _ptr(src_ptr), src_bytes, darr, n, full_h, full_w,
+                                                                 _ptr(mean_ptr), varr, V, _ptr(prob_ptr), _ptr(top5_ptr),
+                                                                 _ptr(prob_views_ptr)))
+
+    def forward_u8_resized_host(self, images, full_hw, mean=None, views=None, descs=None):
         """Blocking convenience: images — a list of uint8 arrays [C][h][w] of differing sizes — are packed, uploaded, resized
         to full_hw = (full_h, full_w) on the device, the float32 mean [C][full_h][full_w] (or None) subtracted, and evaluated on
-        `views` (default: the centre crop alone, which makes the call BmpImgIO::Load + the forward pass).  Returns (prob
-        [n][classes] averaged over the views, top5 [n][5], prob_views [n][len(views)][classes]) as numpy arrays."""
+        `views` (default: the centre crop alone, which makes the call BmpImgIO::Load + the forward pass).  With images = None
+        and descs = (flat, descs) — a uint8 buffer and the SrcPixels of the images in it, as pack_bmp_files / pack_interleaved
+        give them — the buffer is uploaded untouched and read in place.  Returns (prob [n][classes] averaged over the views,
+        top5 [n][5], prob_views [n][len(views)][classes]) as numpy arrays."""
         full_h, full_w = int(full_hw[0]), int(full_hw[1])
         _, in_h, in_w = self.in_chw
         if views is None:
             views = [((full_h - in_h) // 2, (full_w - in_w) // 2, 0)]
-        return self._u8_host(self.forward_u8_resized_views_dev, images, full_h, full_w, mean, "mean image",
-                             (self.in_chw[0], full_h, full_w), views)
+        call = self.forward_u8_resized_views_dev if descs is None else self.forward_u8_resized_views_strided_dev
+        return self._u8_host(call, images, full_h, full_w, mean, "mean image", (self.in_chw[0], full_h, full_w), views, descs)
 
     def forward_u8_relaxed_views_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int, mean_crop_ptr: int | None,
                                      views, prob_ptr: int | None = None, top5_ptr: int | None = None,
@@ -301,21 +345,42 @@ class QcnnEngine:
                                                          _ptr(mean_crop_ptr), varr, V, _ptr(prob_ptr), _ptr(top5_ptr),
                                                          _ptr(prob_views_ptr)))
 
-    def forward_u8_relaxed_host(self, images, full_hw, mean_crop=None, views=None):
+    def forward_u8_relaxed_views_strided_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int,
+                                             mean_crop_ptr: int | None, views, prob_ptr: int | None = None,
+                                             top5_ptr: int | None = None, prob_views_ptr: int | None = None):
+        """forward_u8_relaxed_views_dev on source images read in place (qcnn_forward_u8_relaxed_views_strided); descs as
+        forward_u8_resized_views_strided_dev takes them."""
+        darr, n = _pixels_array(descs)
+        varr, V = _struct_array(capi.QcnnAnchorView, views)
+        self._chk(self.lib.qcnn_forward_u8_relaxed_views_strided(self.h, _ptr(src_ptr), src_bytes, darr, n, full_h, full_w,
+                                                                 _ptr(mean_crop_ptr), varr, V, _ptr(prob_ptr), _ptr(top5_ptr),
+                                                                 _ptr(prob_views_ptr)))
+
+    def forward_u8_relaxed_host(self, images, full_hw, mean_crop=None, views=None, descs=None):
         """Blocking convenience: images — a list of uint8 arrays [C][h][w] of differing sizes — are packed, uploaded, resized
         by one scale each towards full_hw = (full_h, full_w) on the device, cropped, the float32 mean_crop [C][in_h][in_w] (or
         None) subtracted, and evaluated on `views` (default: the centre anchor alone, which makes the call BmpImgIO::Load of a
-        Relaxed / Crop model + the forward pass).  Returns (prob [n][classes] averaged over the views, top5 [n][5], prob_views
-        [n][len(views)][classes]) as numpy arrays."""
+        Relaxed / Crop model + the forward pass).  images = None and descs = (flat, descs): as forward_u8_resized_host.
+        Returns (prob [n][classes] averaged over the views, top5 [n][5], prob_views [n][len(views)][classes]) as numpy
+        arrays."""
         if views is None:
             views = [(1, 1, 0, 0, 0)]
-        return self._u8_host(self.forward_u8_relaxed_views_dev, images, int(full_hw[0]), int(full_hw[1]), mean_crop, "crop mean",
-                             tuple(self.in_chw), views)
+        call = self.forward_u8_relaxed_views_dev if descs is None else self.forward_u8_relaxed_views_strided_dev
+        return self._u8_host(call, images, int(full_hw[0]), int(full_hw[1]), mean_crop, "crop mean", tuple(self.in_chw), views, descs)
 
-    def _u8_host(self, call, images, full_h, full_w, mean, mean_name, mean_shape, views):
-        """The blocking 8-bit calls around their asynchronous one: pack and upload, `call`, wait, download."""
+    def _u8_host(self, call, images, full_h, full_w, mean, mean_name, mean_shape, views, given=None):
+        """The blocking 8-bit calls around their asynchronous one: pack (or take the caller's buffer and descriptors) and
+        upload, `call`, wait, download."""
         import torch   # plumbing only: device buffers and copies
-        flat, descs = pack_sources(images)
+        if given is not None and images is not None:
+            raise ValueError("images and descs=(flat, descs) exclude each other")
+        if given is not None:
+            flat, descs = np.asarray(given[0]), list(given[1])
+            if flat.dtype != np.uint8 or flat.ndim != 1 or not flat.size or not descs:
+                raise ValueError("descs=(flat, descs): a non-empty one-dimensional uint8 buffer and its descriptors")
+            flat = np.ascontiguousarray(flat)
+        else:
+            flat, descs = pack_sources(images)
         n, V = len(descs), len(views)
         fh, fw, fc = self.fm_dims(self.L)
         classes = fh * fw * fc
@@ -463,6 +528,66 @@ def pack_sources(images):
     flat = np.empty(off, np.uint8)
     for a, (o, _, _) in zip(imgs, descs):
         flat[o:o + a.size] = a.reshape(-1)
+    return flat, descs
+
+
+def src_planar(offset: int, h: int, w: int, C: int) -> SrcPixels:
+    """The SrcPixels of a planar [C][h][w] image at `offset` (qcnn_src_planar): what pack_sources' (offset, h, w) means.  Needs
+    no device."""
+    return _src_planar(int(offset), int(h), int(w), int(C))
+
+
+def _src_planar(offset, h, w, channels):              # `C` is ctypes here
+    out = capi.QcnnSrcPixels()
+    if capi.load().qcnn_src_planar(C.byref(capi.QcnnSrcImage(offset, h, w)), channels, C.byref(out)):
+        raise QcnnError("src_planar: %d x %dx%d at offset %d is refused (1 to 4 channels, sides of at least 1, under 2 GiB)" % (channels, h, w, offset))
+    return _from_c(out)
+
+
+def src_bmp(file_bytes, file_offset: int = 0) -> SrcPixels:
+    """The SrcPixels of the pixel array of a BMP file whose bytes will lie at `file_offset` of the source buffer (qcnn_src_bmp):
+    24 or 32 bits per pixel, uncompressed, bottom-up or top-down — the flavours BmpImgIO decodes.  Needs no device."""
+    data = bytes(file_bytes)
+    out = capi.QcnnSrcPixels()
+    if capi.load().qcnn_src_bmp(data, len(data), int(file_offset), C.byref(out)):
+        raise QcnnError("src_bmp: not a BMP file this library reads in place (BM, 24 or 32 bits per pixel, uncompressed, complete)")
+    return _from_c(out)
+
+
+def pack_bmp_files(files):
+    """A list of BMP files' contents (bytes) -> (flat uint8 buffer with the files back to back, untouched, [SrcPixels]): what
+    the strided calls read once the buffer is on the device.  Needs no device."""
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("pack_bmp_files: no file")
+    descs, off = [], 0
+    for k, f in enumerate(files):
+        try:
+            descs.append(src_bmp(f, off))
+        except QcnnError as e:
+            raise QcnnError("file %d: %s" % (k, e)) from None
+        off += len(f)
+    return np.frombuffer(bytearray(b"".join(files)), np.uint8), descs      # a bytearray: the array is writable, as torch wants it
+
+
+def pack_interleaved(images, order="BGR"):
+    """A list of uint8 arrays [h][w][3] (a decoder's output; order: "BGR" or "RGB", the order of the three bytes of a pixel) ->
+    (flat uint8 buffer with the arrays back to back, untouched, [SrcPixels]).  Needs no device."""
+    if order not in ("BGR", "RGB"):
+        raise ValueError("pack_interleaved: order is 'BGR' or 'RGB'")
+    imgs = list(images)
+    if not imgs:
+        raise ValueError("pack_interleaved: no image")
+    descs, off = [], 0
+    for k, a in enumerate(imgs):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            raise ValueError("pack_interleaved: image %d is not a uint8 array [h][w][3]" % k)
+        h, w = int(a.shape[0]), int(a.shape[1])
+        descs.append(SrcPixels(off, 3 * w, h, w, 3, (0, 1, 2, 0) if order == "BGR" else (2, 1, 0, 0)))
+        off += a.size
+    flat = np.empty(off, np.uint8)
+    for a, d in zip(imgs, descs):
+        flat[d.offset:d.offset + a.size] = a.reshape(-1)
     return flat, descs
 
 
