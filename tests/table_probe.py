@@ -403,6 +403,22 @@ SHAPES = {
     "fcd_d640": ("fc", fc_geom(640, 40), 640, 16, 1, 16),
     "fcd_d768": ("fc", fc_geom(768, 40), 768, 16, 1, 20),
     "fcd_d2048": ("fc", fc_geom(2048, 40), 2048, 16, 1, 52),
+    # the panel conv families (k_conv_aprx tile / sliding, k_conv_sym, k_conv_sym8, k_conv_half8, split tiles + k_conv_sum) on DENSE
+    # sums: a deep sub-space axis (hundreds of stages per tile) on maps of about 7 x 10, knl^2 M <= 1200 everywhere.  PANEL_REACH
+    # states what each one reaches; tests/test_panel_cases_cpu.py re-derives it from the planner's and the launchers' rules
+    "pn_deep": ("conv", conv_geom(7, 10, 128, 3, 1, 1, 1, 128), 32, 128, 4, None),          # 288 terms; every family
+    "pn_c192": ("conv", conv_geom(7, 9, 64, 3, 1, 1, 1, 192), 8, 128, 8, None),
+    "pn_c256_cs4": ("conv", conv_geom(7, 10, 64, 3, 1, 1, 1, 256), 16, 128, 4, None),
+    "pn_c384": ("conv", conv_geom(7, 9, 64, 3, 1, 1, 1, 384), 8, 128, 8, None),
+    "pn_c512": ("conv", conv_geom(7, 10, 128, 3, 1, 1, 1, 512), 16, 128, 8, None),
+    "pn_grp2_5x5": ("conv", conv_geom(11, 7, 128, 5, 1, 2, 2, 256), 8, 128, 8, None),       # alex_conv2 with a deeper axis: 200 terms
+    "pn_s2_5x5": ("conv", conv_geom(13, 9, 128, 5, 2, 2, 1, 128), 16, 128, 8, None),        # 400 terms; 7 x 5 outputs
+    "pn_k32_m18": ("conv", conv_geom(7, 10, 72, 3, 1, 1, 1, 64), 18, 32, 4, None),          # G = 4, last stage of a pixel: 2 sub-spaces
+    "pn_k10_m32": ("conv", conv_geom(7, 10, 128, 3, 1, 1, 1, 32), 32, 10, 4, None),         # G = 12, last stage: 8
+    "pn_k64_m9": ("conv", conv_geom(7, 9, 72, 3, 1, 1, 1, 96), 9, 64, 8, None),             # G = 2, last stage: 1
+    "pn_partial": ("conv", conv_geom(7, 9, 68, 3, 1, 1, 1, 64), 9, 128, 8, None),           # last sub-space: 4 of 8 dims
+    "pn_k200": ("conv", conv_geom(7, 10, 64, 3, 1, 1, 1, 64), 16, 200, 4, None),            # two pseudo sub-spaces per sub-space
+    "pn_k256": ("conv", conv_geom(7, 10, 128, 3, 1, 1, 1, 64), 16, 256, 8, None),           # three
 }
 
 # What the few-image launchers must choose for each of those shapes (qk_conv_small: output tile, sub-spaces per table chunk,
@@ -472,6 +488,83 @@ DEC_NOT = {
     "nd_conv_k200": ("conv", conv_geom(9, 10, 3, 5, 1, 0, 1, 96), 1, 200, 4, None),
     "nd_fc_k130": ("fc", fc_geom(64, 40), 64, 130, 1, None),
 }
+
+
+# What the planner and the launchers of the panel conv kernels must choose for each pn_* shape for the case to reach the seam it is
+# there for.  stage = (G = sub-spaces per LUT stage, sub-spaces of a pixel's LAST stage, stages per source pixel — pseudo
+# sub-spaces counted); live = the families that must run it, by the planner's names, with
+#   tile / sym16 / sym8:          (channels per wave, th, tw, channel chunks per group, (tilesY, tilesX), stages of the heaviest tile)
+#   half8:                        (channels per wave, th, tw, wave sets, chunks, (tilesY, tilesX), stages of the heaviest tile)
+#   slide16 / sym8_slide:         (channels per wave, slots, columns per strip, chunks, strips, stages of the widest whole-column strip)
+#   half8_slide:                  (channels per wave, slots, columns per strip, wave sets, chunks, strips, stages of that strip)
+#   split_tile / split_sym8:      (slices Z, first split tile rank) at ONE panel under QCNN_OPT_SPLIT (the batch of 125 images)
+# dead = the families that must report "not eligible" (cost 0).  Every kernel keeps two LUT stage buffers and two (16-wave) or three
+# (eight-wave, half-panel) program-row buffers: each stage count below wraps all of them many times.
+PANEL_REACH = {
+    # every family and both split forms; 288 terms of 4 dims; 128 channels per group is the one symmetric shape.  Clipped last tiles
+    # in both axes for 2x2 (rows), 2x3 and 3x4; 3 x 3 half-panel tiles: interior / edge / corner ranks; Z = 8 cuts 480 stages at
+    # 60, 120, ... — inside a pixel's 32 stages; Z = 6 does not divide 640
+    "pn_deep": dict(stage=(1, 1, 32),
+                    live={"tile": (12, 1, 3, 1, (7, 4), 480), "slide16": (12, 3, 1, 1, 10, 672), "sym16": (8, 2, 2, 1, (4, 5), 512),
+                          "sym8": (16, 2, 3, 1, (4, 4), 640), "sym8_slide": (16, 3, 2, 1, 5, 896), "half8": (32, 3, 4, 2, 1, (3, 3), 960),
+                          "half8_slide": (32, 3, 4, 2, 1, 3, 1344), "split_tile": (8, 0), "split_sym8": (6, 0)},
+                    dead=()),
+    # the channel configurations of the eight-wave (24 / 32 / 48 channels per wave, two chunks at 512) and the half-panel kernel
+    # (cases 192 / 256 / 384 / 512) and their sliding forms, Cs = 8 and 4; 7 x 9 maps clip the 1x2, 2x2 and 2x4 tiles in both axes
+    "pn_c192": dict(stage=(1, 1, 8),
+                    live={"tile": (16, 1, 2, 1, (7, 5), 96), "slide16": (12, 3, 1, 2, 9, 168), "sym8": (24, 2, 2, 1, (4, 5), 128),
+                          "sym8_slide": (24, 3, 1, 1, 9, 168), "half8": (48, 2, 4, 2, 1, (4, 3), 192),
+                          "half8_slide": (48, 3, 2, 2, 1, 5, 224), "split_tile": (5, 0), "split_sym8": (6, 0)},
+                    dead=("sym16",)),
+    "pn_c256_cs4": dict(stage=(1, 1, 16),
+                        live={"tile": (24, 1, 1, 1, (7, 10), 144), "slide16": (12, 3, 1, 2, 10, 336), "sym8": (32, 1, 3, 1, (7, 4), 240),
+                              "sym8_slide": (32, 3, 1, 1, 10, 336), "half8": (32, 2, 3, 1, 1, (4, 4), 320),
+                              "half8_slide": (32, 3, 2, 1, 1, 5, 448), "split_tile": (3, 0), "split_sym8": (6, 0)},
+                        dead=("sym16",)),
+    "pn_c384": dict(stage=(1, 1, 8),
+                    live={"tile": (32, 1, 1, 1, (7, 9), 72), "slide16": (12, 3, 1, 3, 9, 168), "sym8": (48, 1, 2, 1, (7, 5), 96),
+                          "sym8_slide": (24, 3, 1, 2, 9, 168), "half8": (48, 2, 2, 1, 1, (4, 5), 128),
+                          "half8_slide": (48, 3, 1, 1, 1, 9, 168), "split_tile": (4, 0), "split_sym8": (5, 0)},
+                    dead=("sym16",)),
+    "pn_c512": dict(stage=(1, 1, 16),
+                    live={"tile": (24, 1, 1, 2, (7, 10), 144), "slide16": (12, 3, 1, 4, 10, 336), "sym8": (32, 1, 3, 2, (7, 4), 240),
+                          "sym8_slide": (32, 3, 1, 2, 10, 336), "half8": (64, 1, 3, 1, 1, (7, 4), 240),
+                          "half8_slide": (64, 3, 1, 1, 1, 10, 336), "split_tile": (3, 0), "split_sym8": (4, 0)},
+                    dead=("sym16",)),
+    # two groups, 5x5 / pad 2: five slots — the 16-wave sliding form with 6 channels per wave in two chunks, the eight-wave one with
+    # 16; no half-panel sliding form; 4 x 2 half-panel tiles: the row-major tile numbering; 2x2 tiles clipped in both axes
+    "pn_grp2_5x5": dict(stage=(1, 1, 8),
+                        live={"tile": (12, 1, 3, 1, (11, 3), 240), "slide16": (6, 5, 1, 2, 7, 440), "sym16": (8, 2, 2, 1, (6, 4), 288),
+                              "sym8": (16, 2, 3, 1, (6, 3), 288), "sym8_slide": (16, 5, 1, 1, 7, 440),
+                              "half8": (32, 3, 4, 2, 1, (4, 2), 336), "split_tile": (4, 0), "split_sym8": (6, 0)},
+                        dead=("half8_slide",)),
+    # 5x5 / stride 2 / pad 2 on an odd 13 x 9 map: three slots, every sliding form, the last two-column strip one column wide; two
+    # tiles per row: the row-major numbering of the 16-wave, eight-wave and half-panel tile kernels
+    "pn_s2_5x5": dict(stage=(1, 1, 16),
+                      live={"tile": (12, 1, 3, 1, (7, 2), 560), "slide16": (12, 3, 1, 1, 5, 1040), "sym16": (8, 2, 2, 1, (4, 3), 784),
+                            "sym8": (16, 2, 3, 1, (4, 2), 784), "sym8_slide": (16, 3, 2, 1, 3, 1456),
+                            "half8": (32, 3, 4, 2, 1, (3, 2), 1296), "half8_slide": (32, 3, 4, 2, 1, 2, 1872), "split_tile": (8, 0),
+                            "split_sym8": (6, 0)},
+                      dead=()),
+    # K < 128: G sub-spaces per stage, M % G != 0 — the last stage of every pixel is ragged; Z = 3 cuts between the stage groups of a
+    # pixel.  Only the 16-wave tile kernel takes them (the sliding program is built for K = 128 alone); tiles 2x3, 2x4, 2x2
+    "pn_k32_m18": dict(stage=(4, 2, 5), live={"tile": (6, 2, 3, 1, (4, 4), 100), "split_tile": (3, 0)},
+                       dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide")),
+    "pn_k10_m32": dict(stage=(12, 8, 3), live={"tile": (4, 2, 4, 1, (4, 3), 72), "split_tile": (3, 0)},
+                       dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide")),
+    "pn_k64_m9": dict(stage=(2, 1, 5), live={"tile": (8, 2, 2, 1, (4, 5), 80), "split_tile": (3, 0)},
+                      dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide")),
+    # 4 of 8 dims in the last sub-space: operand masks; no eight-wave, half-panel or symmetric form; two-column strips of the 16-wave
+    # sliding form, the last one a single column
+    "pn_partial": dict(stage=(1, 1, 9), live={"tile": (6, 2, 3, 1, (4, 3), 180), "slide16": (6, 3, 2, 1, 5, 252), "split_tile": (8, 0)},
+                       dead=("sym16", "sym8", "sym8_slide", "half8", "half8_slide")),
+    # K > 128: two / three pseudo sub-spaces per sub-space, the exact-builder tile kernel under every option
+    "pn_k200": dict(stage=(1, 1, 32), live={"tile": (6, 2, 3, 1, (4, 4), 640)},
+                    dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide")),
+    "pn_k256": dict(stage=(1, 1, 48), live={"tile": (6, 2, 3, 1, (4, 4), 960)},
+                    dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide")),
+}
+PANEL_BATCH, PANEL_HALF_BATCHES, PANEL_SPLIT_BATCH = 131, (70, 5), 125     # a full panel + a ragged one of three; half panels; one panel
 
 
 def dec_dense_rel(kind, g, split_bf16=False):
