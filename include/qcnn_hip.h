@@ -455,6 +455,50 @@ int qcnn_forward_host(QcnnCtx* ctx, const float* in_nchw_host, int n, float* pro
  * registered (qcnn_host_register) or pinned input memory the kernels never wait for PCIe. */
 int qcnn_forward_host_batches(QcnnCtx* ctx, const float* const* in_host, const int* n, int nb, float* const* prob_host,
                               uint16_t* const* top5_host);
+/* The same schedule for 8-bit SOURCE images in host memory: what the reference's image loop does with a labelled set of files
+ * (src/CaffeEva.cc:151-211: load, pre-process, classify batch after batch; :263-295: count the hits), with BmpImgIO::Load's
+ * resize, mean and crop on the device.  A batch is its source bytes as they lie — BMP files, planar or interleaved images,
+ * frames — and n descriptors whose offsets are relative to src_host (qcnn_src_planar / qcnn_src_bmp make them).  A 256 x 256
+ * x 3 source is 196 608 bytes against the 618 348 of AlexNet's float crop, and with n_views views one source feeds n_views
+ * batch slots.
+ * Both calls are BLOCKING and mean qcnn_forward_u8_resized_views_strided / qcnn_forward_u8_relaxed_views_strided applied batch
+ * after batch: prob_host [n][classes] and top5_host [n][5] are those of the view average, prob_views_host [n][n_views][classes]
+ * the un-averaged rows, each bit for bit what the strided call writes for that batch; mean, views, full size as there.
+ * Schedule: the source bytes (and labels) of batch b + 1 go up on the copy stream into one of two device buffers the context
+ * owns (allocated at first use, grown — before the first upload of a call — when a call's largest src_bytes needs more, freed
+ * with the context), under the layers of batch b; a buffer is handed back behind the PACK kernel of its batch, its last
+ * reader; results return through pinned buffers one batch late.  No float input is ever staged.  With src_host in pinned
+ * (qcnn_host_alloc) or registered memory the kernels never wait for PCIe; pageable memory is correct and slower.
+ * labels: n ground-truth classes, or NULL = the batch is not counted.  hits5 (or NULL: nothing is counted) receives
+ * CaffeEva::CalcPredAccu's five counters BEFORE its running sum (src/CaffeEva.cc:276-286) over the labelled batches of this
+ * call: hits5[r] = #{ i : top5[i][r] == labels[i] } on the view-averaged top-5, one label per IMAGE (not per slot), every rank
+ * tested by itself — a row that repeats a class (the reference's rows do, with class 0, once fewer than five probabilities
+ * exceed FLT_MIN) counts it at every rank where it stands.  ACCURACY@k as Main.cc prints it is the CALLER's running sum
+ * hits5[0] + ... + hits5[k-1] over the number of labelled images.  Counting happens on the device behind each labelled
+ * batch's top-5 (qcnn_count_top5_hits into a counter block the context owns, zeroed at entry) with no host round trip per
+ * batch; the five numbers are read back once, at the end.
+ * Every batch is checked before anything is enqueued or any buffer rewritten — non-zero, a message that names the batch and
+ * the image ("batch 3: image 17: ..."), every host output and hits5 untouched: nb <= 0, a NULL batches / views / src_host /
+ * imgs, n <= 0, n * n_views > max_batch, every descriptor against its OWN batch's src_bytes and every view as the strided
+ * calls check them, a label >= classes.  QCNN_DEBUG_PIPELINE=1 in the environment prints the schedule (upload and layer
+ * intervals per batch) to stderr, as for qcnn_forward_host_batches. */
+typedef struct QcnnU8Batch {
+  const uint8_t* src_host; size_t src_bytes;   /* the batch's source bytes as they lie */
+  const QcnnSrcPixels* imgs; int n;            /* n descriptors, offsets relative to src_host */
+  const uint16_t* labels;                      /* n ground-truth classes, or NULL: batch not counted */
+  float* prob_host; uint16_t* top5_host; float* prob_views_host;   /* each may be NULL */
+} QcnnU8Batch;
+int qcnn_forward_u8_resized_host_batches(QcnnCtx* ctx, const QcnnU8Batch* batches, int nb, int full_h, int full_w,
+                                         const float* mean_dev /* [C][full_h][full_w] or NULL */,
+                                         const QcnnView* views_host, int n_views, unsigned long long hits5[5] /* or NULL */);
+int qcnn_forward_u8_relaxed_host_batches(QcnnCtx* ctx, const QcnnU8Batch* batches, int nb, int full_h, int full_w,
+                                         const float* mean_crop_dev /* [C][in_h][in_w] or NULL */,
+                                         const QcnnAnchorView* views_host, int n_views, unsigned long long hits5[5] /* or NULL */);
+/* The counting alone, asynchronous on the context's stream, DEVICE pointers: hits5_dev[r] += #{ i < n : top5_dev[i * 5 + r] ==
+ * labels_dev[i] } for r = 0..4 — accumulated INTO the five counters, which the caller zeroes.  Integer sums: the same from run
+ * to run.  Non-zero for a NULL pointer or n <= 0. */
+int qcnn_count_top5_hits(QcnnCtx* ctx, const uint16_t* top5_dev, const uint16_t* labels_dev, int n,
+                         unsigned long long* hits5_dev /* [5], accumulated into */);
 /* Pin / unpin caller memory (hipHostRegister, portable across devices) so that uploads from it are asynchronous DMA
  * transfers.  Errors are reported through qcnn_last_error(NULL). */
 int qcnn_host_register(void* ptr, size_t bytes);

@@ -49,6 +49,13 @@ class QcnnAnchorView(C.Structure):
     _fields_ = [("ay", C.c_int), ("ax", C.c_int), ("dy", C.c_int), ("dx", C.c_int), ("flip", C.c_int)]
 
 
+class QcnnU8Batch(C.Structure):
+    """One batch of qcnn_forward_u8_*_host_batches: its source bytes in host memory as they lie, n descriptors with offsets
+    relative to src_host, n labels or NULL (batch not counted), and the three host outputs, each of which may be NULL."""
+    _fields_ = [("src_host", C.c_void_p), ("src_bytes", C.c_size_t), ("imgs", C.POINTER(QcnnSrcPixels)), ("n", C.c_int),
+                ("labels", C.c_void_p), ("prob_host", C.c_void_p), ("top5_host", C.c_void_p), ("prob_views_host", C.c_void_p)]
+
+
 def layer_desc(ly: dict) -> QcnnLayerDesc:
     return QcnnLayerDesc(ly["type"], ly.get("pad", 0), ly.get("knl", 0), ly.get("cnt", 0), ly.get("grp", 0),
                          ly.get("stride", 0), ly.get("nod", 0), ly.get("siz", 0), ly.get("alp", 0.0),
@@ -113,6 +120,11 @@ def load():
                                                           C.POINTER(QcnnAnchorView), i, f32p, u16p, f32p]
     lib.qcnn_forward_host.argtypes = [vp, f32p, i, f32p, u16p]
     lib.qcnn_forward_host_batches.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp)]
+    lib.qcnn_forward_u8_resized_host_batches.argtypes = [vp, C.POINTER(QcnnU8Batch), i, i, i, f32p, C.POINTER(QcnnView), i,
+                                                         C.POINTER(C.c_ulonglong)]
+    lib.qcnn_forward_u8_relaxed_host_batches.argtypes = [vp, C.POINTER(QcnnU8Batch), i, i, i, f32p, C.POINTER(QcnnAnchorView), i,
+                                                         C.POINTER(C.c_ulonglong)]
+    lib.qcnn_count_top5_hits.argtypes = [vp, u16p, u16p, i, vp]
     lib.qcnn_host_register.argtypes = [vp, C.c_size_t]
     lib.qcnn_host_unregister.argtypes = [vp]
     lib.qcnn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]

@@ -136,6 +136,22 @@ struct QcnnCtx {
   struct SrcStage { void* pin = nullptr; void* dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
   SrcStage srcStage[2];
   int srcStageNext = 0;
+  // qcnn_forward_u8_*_host_batches: source bytes stream host -> device through two buffers the context owns like viewMean
+  // (first use, grown when a call needs more, freed with the context); everything sized by max_batch and the classes goes with
+  // the model (free_model).  No float input staging: the pack kernel reads the source bytes in place
+  struct U8Stream {
+    uint8_t* src[2] = {nullptr, nullptr};
+    size_t srcCap = 0;
+    hipEvent_t evCounted[2] = {nullptr, nullptr};     // "the hit count that read labels[k] has passed"
+    uint16_t* labels[2] = {nullptr, nullptr};         // [maxBatch] on the device
+    uint16_t* pinLabels[2] = {nullptr, nullptr};
+    float* prob = nullptr;                            // [maxBatch][classes]: the view averages
+    float* rows = nullptr;                            // [maxBatch][classes]: the un-averaged rows of n * V <= maxBatch slots
+    uint16_t* top5 = nullptr;
+    float* pinRows[2] = {nullptr, nullptr};
+    unsigned long long* hits = nullptr;               // [5] on the device, zeroed at every call's entry
+    unsigned long long* pinHits = nullptr;
+  } u8s;
   int lastN = 0;
   std::vector<float*> lastFm;        // pointer table of the last forward
 
@@ -385,6 +401,21 @@ void free_model(QcnnCtx* c) {
     if (c->pinTop5[k]) (void)hipHostFree(c->pinTop5[k]);
     c->pinProb[k] = nullptr; c->pinTop5[k] = nullptr; c->freedValid[k] = false;
   }
+  {
+    QcnnCtx::U8Stream& s = c->u8s;                      // what is sized by the model; the source buffers stay
+    for (int k = 0; k < 2; ++k) {
+      if (s.labels[k]) (void)hipFree(s.labels[k]);
+      if (s.pinLabels[k]) (void)hipHostFree(s.pinLabels[k]);
+      if (s.pinRows[k]) (void)hipHostFree(s.pinRows[k]);
+      s.labels[k] = nullptr; s.pinLabels[k] = nullptr; s.pinRows[k] = nullptr;
+    }
+    if (s.prob) (void)hipFree(s.prob);
+    if (s.rows) (void)hipFree(s.rows);
+    if (s.top5) (void)hipFree(s.top5);
+    if (s.hits) (void)hipFree(s.hits);
+    if (s.pinHits) (void)hipHostFree(s.pinHits);
+    s.prob = s.rows = nullptr; s.top5 = nullptr; s.hits = s.pinHits = nullptr;
+  }
   if (c->fcPartial) (void)hipFree(c->fcPartial);
   if (c->convPartial) (void)hipFree(c->convPartial);
   c->convPartial = nullptr; c->noConvPartial = false;
@@ -426,21 +457,56 @@ int ensure_stage(QcnnCtx* c, size_t elems = 0) {
   return 0;
 }
 
-// buffers, stream and events of the pipelined host path
-int ensure_pipeline(QcnnCtx* c) {
-  if (ensure_stage(c)) return 1;
-  if (c->stageIn1) return 0;
-  const size_t inElems = fm_elems(c, 0) * c->maxBatch;
+// events and pinned result buffers of the pipelined host paths: all the 8-bit stream takes of them
+int ensure_pipeline_results(QcnnCtx* c) {
   const size_t classes = fm_elems(c, c->L);
   for (int k = 0; k < 2; ++k) {
     if (!c->evCopied[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->evCopied[k], hipEventDisableTiming));
-    if (!c->evFreed[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->evFreed[k], hipEventDisableTiming));
+    if (!c->evFreed[k]) { HIP_TRY(c, hipEventCreateWithFlags(&c->evFreed[k], hipEventDisableTiming)); c->freedValid[k] = false; }
     if (!c->evDone[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->evDone[k], hipEventDisableTiming));
-    HIP_TRY(c, hipHostMalloc(&c->pinProb[k], (size_t)c->maxBatch * classes * sizeof(float), hipHostMallocPortable));
-    HIP_TRY(c, hipHostMalloc(&c->pinTop5[k], (size_t)c->maxBatch * 5 * sizeof(uint16_t), hipHostMallocPortable));
-    c->freedValid[k] = false;
+    if (!c->pinProb[k]) HIP_TRY(c, hipHostMalloc(&c->pinProb[k], (size_t)c->maxBatch * classes * sizeof(float), hipHostMallocPortable));
+    if (!c->pinTop5[k]) HIP_TRY(c, hipHostMalloc(&c->pinTop5[k], (size_t)c->maxBatch * 5 * sizeof(uint16_t), hipHostMallocPortable));
   }
-  HIP_TRY(c, hipMalloc(&c->stageIn1, inElems * sizeof(float) + kSlack));
+  return 0;
+}
+
+// buffers, stream and events of the pipelined float path: the results' and the two device input buffers
+int ensure_pipeline(QcnnCtx* c) {
+  if (ensure_stage(c)) return 1;
+  if (c->stageIn1) return 0;
+  if (ensure_pipeline_results(c)) return 1;
+  HIP_TRY(c, hipMalloc(&c->stageIn1, fm_elems(c, 0) * c->maxBatch * sizeof(float) + kSlack));
+  return 0;
+}
+
+// what the 8-bit stream owns beside them: two source buffers of at least srcBytes, and per model the label pairs, the device
+// results, the pinned pair of the un-averaged rows and the hit counters.  The source buffers grow here, in front of the
+// first upload of a call, never inside a stream
+int ensure_u8_stream(QcnnCtx* c, size_t srcBytes) {
+  if (ensure_pipeline_results(c)) return 1;
+  QcnnCtx::U8Stream& s = c->u8s;
+  const size_t rowBytes = (size_t)c->maxBatch * fm_elems(c, c->L) * sizeof(float), labelBytes = (size_t)c->maxBatch * sizeof(uint16_t);
+  for (int k = 0; k < 2; ++k) {
+    if (!s.evCounted[k]) HIP_TRY(c, hipEventCreateWithFlags(&s.evCounted[k], hipEventDisableTiming));
+    if (!s.labels[k]) HIP_TRY(c, hipMalloc(&s.labels[k], labelBytes));
+    if (!s.pinLabels[k]) HIP_TRY(c, hipHostMalloc(&s.pinLabels[k], labelBytes, hipHostMallocPortable));
+    if (!s.pinRows[k]) HIP_TRY(c, hipHostMalloc(&s.pinRows[k], rowBytes, hipHostMallocPortable));
+  }
+  if (!s.prob) HIP_TRY(c, hipMalloc(&s.prob, rowBytes));
+  if (!s.rows) HIP_TRY(c, hipMalloc(&s.rows, rowBytes));
+  if (!s.top5) HIP_TRY(c, hipMalloc(&s.top5, (size_t)c->maxBatch * 5 * sizeof(uint16_t)));
+  if (!s.hits) HIP_TRY(c, hipMalloc(&s.hits, 5 * sizeof(unsigned long long)));
+  if (!s.pinHits) HIP_TRY(c, hipHostMalloc(&s.pinHits, 5 * sizeof(unsigned long long), hipHostMallocPortable));
+  if (s.srcCap >= srcBytes && s.src[0] && s.src[1]) return 0;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));          // grow: an earlier pack kernel may still be reading the old buffers
+  HIP_TRY(c, hipStreamSynchronize(c->copyStream));
+  for (int k = 0; k < 2; ++k) {
+    if (s.src[k]) (void)hipFree(s.src[k]);
+    s.src[k] = nullptr;
+  }
+  s.srcCap = 0;                                          // committed only when BOTH buffers exist
+  for (int k = 0; k < 2; ++k) HIP_TRY(c, hipMalloc(&s.src[k], srcBytes + kSlack));
+  s.srcCap = srcBytes;
   return 0;
 }
 
@@ -957,6 +1023,10 @@ int qcnn_ctx_destroy(QcnnCtx* c) {
   (void)hipStreamSynchronize(c->stream);
   free_model(c);
   if (c->viewMean) (void)hipFree(c->viewMean);
+  for (int k = 0; k < 2; ++k) {
+    if (c->u8s.src[k]) (void)hipFree(c->u8s.src[k]);
+    if (c->u8s.evCounted[k]) (void)hipEventDestroy(c->u8s.evCounted[k]);
+  }
   for (QcnnCtx::SrcStage& g : c->srcStage) {
     if (g.pin) (void)hipHostFree(g.pin);
     if (g.dev) (void)hipFree(g.dev);
@@ -1829,9 +1899,10 @@ QkLayout layout_of(const QcnnSrcPixels& s) {
 }
 // Stage n descriptors D — fill(i) makes image i's — and launch the pack kernel that reads them.  Called when every argument
 // is good: nothing is taken or rewritten for a call that is refused.  The set is marked in flight only once nothing of the
-// host's can fail any more, and its event is recorded behind its one reader.
+// host's can fail any more, and its event is recorded behind its one reader.  afterPack (or nullptr): a second event recorded
+// there — the pack kernel is the last reader of the source buffer too (the streamed calls hand the buffer back on it).
 extern "C++" template <class D, class Fill, class Launch>
-int stage_and_pack(QcnnCtx* c, int n, bool wantMean, Fill fill, Launch launch) {
+int stage_and_pack(QcnnCtx* c, int n, bool wantMean, hipEvent_t afterPack, Fill fill, Launch launch) {
   QcnnCtx::SrcStage* g = stage_take(c, (size_t)n, sizeof(D));
   if (!g) return 1;
   D* pin = static_cast<D*>(g->pin);
@@ -1842,6 +1913,7 @@ int stage_and_pack(QcnnCtx* c, int n, bool wantMean, Fill fill, Launch launch) {
   hipError_t e = launch(static_cast<const D*>(g->dev));
   if (e != hipSuccess) return fail(c, "input pack launch failed: %s", hipGetErrorString(e));
   HIP_TRY(c, hipEventRecord(g->ev, c->stream));
+  if (afterPack) HIP_TRY(c, hipEventRecord(afterPack, c->stream));
   return 0;
 }
 }  // namespace
@@ -1877,44 +1949,110 @@ hipError_t pack_relaxed(const uint8_t* in, const QkRelaxedPixels* d, const float
                         int C, int H, int W, hipStream_t st) { return qk_pack_u8_relaxed_strided(in, d, mean, dst, n, V, views, C, H, W, st); }
 }  // extern "C++"
 
-// qcnn_forward_u8_resized_views (Src = QcnnSrcImage) and qcnn_forward_u8_resized_views_strided (Src = QcnnSrcPixels).
-extern "C++" template <class Src>
-int resized_views(QcnnCtx* c, const char* fn, const uint8_t* src_dev, size_t src_bytes, const Src* imgs_host, int n, int full_h,
-                  int full_w, const float* mean_dev, const QcnnView* views_host, int n_views, float* prob_dev, uint16_t* top5_dev,
-                  float* prob_views_dev) {
-  if (views_open(c, fn, src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views", n, n_views) ||
-      full_image_ok(c, full_h, full_w))
-    return 1;
-  QkViews views = {};
-  if (crop_views(c, views_host, n_views, full_h, full_w, "full", &views)) return 1;
-  for (int i = 0; i < n; ++i)
-    if (src_ok(c, i, imgs_host[i], src_bytes, 1)) return 1;
-  using D = decltype(staged(imgs_host[0], QkSrcImage{}));
+// What the two pre-processing modes differ in: the caller's view type and its check, the check of one source image, the staged
+// descriptor and the pack launch.  Everything around them — one batch on the device (u8_views) and batches streamed from host
+// memory (u8_host_batches) — is written once.
+extern "C++" {
+// ENUM_ReszType::Strict: every image to full_h x full_w, the views cut from that (qcnn_forward_u8_resized_views*)
+struct StrictMode {
+  using View = QcnnView;
+  using Views = QkViews;
+  static int views(QcnnCtx* c, const View* views_host, int n_views, int full_h, int full_w, Views* out) {
+    return crop_views(c, views_host, n_views, full_h, full_w, "full", out);
+  }
+  template <class Src>
+  static int image(QcnnCtx* c, int i, const Src& s, size_t src_bytes, int, int, const Views&, int) { return src_ok(c, i, s, src_bytes, 1); }
+  template <class Src> static auto desc(const Src& s, int full_h, int full_w) {   // the scales: one IEEE division each, as ReszImg computes them
+    return staged(s, QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)});
+  }
+  template <class D>
+  static hipError_t pack(QcnnCtx* c, const uint8_t* src_dev, const D* d, const float* mean_dev, int n, int n_views, const Views& views,
+                         int full_h, int full_w) {
+    return pack_resized(src_dev, d, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
+  }
+};
+// ENUM_ReszType::Relaxed + ENUM_MeanType::Crop: one scale per image, its own full size, anchored views (qcnn_forward_u8_relaxed_views*)
+struct RelaxedMode {
+  using View = QcnnAnchorView;
+  using Views = QkAnchorViews;
+  static int views(QcnnCtx* c, const View* views_host, int n_views, int, int, Views* out) {
+    for (int v = 0; v < n_views; ++v) {
+      const QcnnAnchorView& q = views_host[v];
+      if (q.ay < 0 || q.ay > 2 || q.ax < 0 || q.ax > 2) return fail(c, "view %d: anchors (%d, %d) outside 0..2", v, q.ay, q.ax);
+      out->v[v] = QkAnchorView{q.ay, q.ax, q.dy, q.dx, q.flip ? 1 : 0};
+    }
+    return 0;
+  }
+  template <class Src>
+  static int image(QcnnCtx* c, int i, const Src& s, size_t src_bytes, int full_h, int full_w, const Views& views, int n_views) {
+    if (src_ok(c, i, s, src_bytes, 2)) return 1;
+    int hf = 0, wf = 0;
+    if (qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &hf, &wf, nullptr))
+      return fail(c, "image %d: %dx%d resized towards %dx%d has a side of 2^24 pixels or more", i, s.h, s.w, full_h, full_w);
+    for (int v = 0; v < n_views; ++v) {               // in 64 bits: d is the caller's
+      const QkAnchorView& q = views.v[v];
+      const long long oy = (((long long)(hf - c->inH) * q.ay) >> 1) + q.dy, ox = (((long long)(wf - c->inW) * q.ax) >> 1) + q.dx;
+      if (hf < c->inH || wf < c->inW || oy < 0 || ox < 0 || oy > hf - c->inH || ox > wf - c->inW)
+        return fail(c, "image %d, view %d: the %dx%d crop at (%lld, %lld) leaves the image's %dx%d full size (source %dx%d)", i, v, c->inH,
+                    c->inW, oy, ox, hf, wf, s.h, s.w);
+    }
+    return 0;
+  }
+  template <class Src> static auto desc(const Src& s, int full_h, int full_w) {   // each image's scale and full size
+    QkRelaxedImage d = {s.offset, s.h, s.w, 0.0f, 0, 0, 0};
+    (void)qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &d.hf, &d.wf, &d.s);     // succeeded in image()
+    return staged(s, d);
+  }
+  template <class D>
+  static hipError_t pack(QcnnCtx* c, const uint8_t* src_dev, const D* d, const float* mean_crop_dev, int n, int n_views, const Views& views,
+                         int, int) {
+    return pack_relaxed(src_dev, d, mean_crop_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, c->stream);
+  }
+};
+
+// One checked batch whose source bytes lie on the device: descriptors staged, pack kernel, layers, averaging, outputs — all
+// on the context's stream.  afterPack: stage_and_pack's.
+template <class Mode, class Src>
+int u8_enqueue(QcnnCtx* c, const uint8_t* src_dev, const Src* imgs_host, int n, int full_h, int full_w, const float* mean_dev,
+               const typename Mode::Views& views, int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev,
+               hipEvent_t afterPack) {
+  using D = decltype(Mode::desc(imgs_host[0], full_h, full_w));
   if (stage_and_pack<D>(
-          c, n, prob_dev || top5_dev,
-          [&](int i) {                                // the scales: one IEEE division each, as ReszImg computes them
-            const Src& s = imgs_host[i];
-            return staged(s, QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)});
-          },
-          [&](const D* desc) {
-            return pack_resized(src_dev, desc, mean_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, full_h, full_w, c->stream);
-          }))
+          c, n, prob_dev || top5_dev, afterPack, [&](int i) { return Mode::desc(imgs_host[i], full_h, full_w); },
+          [&](const D* d) { return Mode::pack(c, src_dev, d, mean_dev, n, n_views, views, full_h, full_w); }))
     return 1;
   return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
 }
+
+// qcnn_forward_u8_resized_views[_strided] (Mode = StrictMode) and qcnn_forward_u8_relaxed_views[_strided] (RelaxedMode), for
+// planar (Src = QcnnSrcImage) and strided (QcnnSrcPixels) descriptors.
+template <class Mode, class Src>
+int u8_views(QcnnCtx* c, const char* fn, const uint8_t* src_dev, size_t src_bytes, const Src* imgs_host, int n, int full_h, int full_w,
+             const float* mean_dev, const typename Mode::View* views_host, int n_views, float* prob_dev, uint16_t* top5_dev,
+             float* prob_views_dev) {
+  if (views_open(c, fn, src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views", n, n_views) ||
+      full_image_ok(c, full_h, full_w))
+    return 1;
+  typename Mode::Views views = {};
+  if (Mode::views(c, views_host, n_views, full_h, full_w, &views)) return 1;
+  for (int i = 0; i < n; ++i)
+    if (Mode::image(c, i, imgs_host[i], src_bytes, full_h, full_w, views, n_views)) return 1;
+  return u8_enqueue<Mode>(c, src_dev, imgs_host, n, full_h, full_w, mean_dev, views, n_views, prob_dev, top5_dev, prob_views_dev, nullptr);
+}
+}  // extern "C++"
 }  // namespace
 
 int qcnn_forward_u8_resized_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
                                   int full_h, int full_w, const float* mean_dev, const QcnnView* views_host, int n_views,
                                   float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  return resized_views(c, "qcnn_forward_u8_resized_views", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host, n_views,
+  return u8_views<StrictMode>(c, "qcnn_forward_u8_resized_views", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host, n_views,
                        prob_dev, top5_dev, prob_views_dev);
 }
 
 int qcnn_forward_u8_resized_views_strided(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcPixels* imgs_host, int n,
                                           int full_h, int full_w, const float* mean_dev, const QcnnView* views_host, int n_views,
                                           float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  return resized_views(c, "qcnn_forward_u8_resized_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host,
+  return u8_views<StrictMode>(c, "qcnn_forward_u8_resized_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host,
                        n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
@@ -1945,63 +2083,17 @@ int qcnn_relaxed_full_size(int h, int w, int full_h, int full_w, int* hf, int* w
   return 0;
 }
 
-namespace {
-// qcnn_forward_u8_relaxed_views (Src = QcnnSrcImage) and qcnn_forward_u8_relaxed_views_strided (Src = QcnnSrcPixels).
-extern "C++" template <class Src>
-int relaxed_views(QcnnCtx* c, const char* fn, const uint8_t* src_dev, size_t src_bytes, const Src* imgs_host, int n, int full_h,
-                  int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views, float* prob_dev,
-                  uint16_t* top5_dev, float* prob_views_dev) {
-  if (views_open(c, fn, src_dev && imgs_host && views_host ? nullptr : "source buffer, images or views", n, n_views) ||
-      full_image_ok(c, full_h, full_w))
-    return 1;
-  QkAnchorViews views = {};
-  for (int v = 0; v < n_views; ++v) {
-    const QcnnAnchorView& q = views_host[v];
-    if (q.ay < 0 || q.ay > 2 || q.ax < 0 || q.ax > 2) return fail(c, "view %d: anchors (%d, %d) outside 0..2", v, q.ay, q.ax);
-    views.v[v] = QkAnchorView{q.ay, q.ax, q.dy, q.dx, q.flip ? 1 : 0};
-  }
-  for (int i = 0; i < n; ++i) {
-    const Src& s = imgs_host[i];
-    if (src_ok(c, i, s, src_bytes, 2)) return 1;
-    int hf = 0, wf = 0;
-    if (qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &hf, &wf, nullptr))
-      return fail(c, "image %d: %dx%d resized towards %dx%d has a side of 2^24 pixels or more", i, s.h, s.w, full_h, full_w);
-    for (int v = 0; v < n_views; ++v) {               // in 64 bits: d is the caller's
-      const QkAnchorView& q = views.v[v];
-      const long long oy = (((long long)(hf - c->inH) * q.ay) >> 1) + q.dy, ox = (((long long)(wf - c->inW) * q.ax) >> 1) + q.dx;
-      if (hf < c->inH || wf < c->inW || oy < 0 || ox < 0 || oy > hf - c->inH || ox > wf - c->inW)
-        return fail(c, "image %d, view %d: the %dx%d crop at (%lld, %lld) leaves the image's %dx%d full size (source %dx%d)", i, v, c->inH,
-                    c->inW, oy, ox, hf, wf, s.h, s.w);
-    }
-  }
-  using D = decltype(staged(imgs_host[0], QkRelaxedImage{}));
-  if (stage_and_pack<D>(
-          c, n, prob_dev || top5_dev,
-          [&](int i) {                                // each image's scale and full size
-            const Src& s = imgs_host[i];
-            QkRelaxedImage d = {s.offset, s.h, s.w, 0.0f, 0, 0, 0};
-            (void)qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &d.hf, &d.wf, &d.s);     // succeeded above
-            return staged(s, d);
-          },
-          [&](const D* desc) {
-            return pack_relaxed(src_dev, desc, mean_crop_dev, c->fmBuf[0], n, n_views, views, c->inC, c->inH, c->inW, c->stream);
-          }))
-    return 1;
-  return views_tail(c, n, n_views, prob_dev, top5_dev, prob_views_dev);
-}
-}  // namespace
-
 int qcnn_forward_u8_relaxed_views(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcImage* imgs_host, int n,
                                   int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
                                   float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  return relaxed_views(c, "qcnn_forward_u8_relaxed_views", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev, views_host,
+  return u8_views<RelaxedMode>(c, "qcnn_forward_u8_relaxed_views", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev, views_host,
                        n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
 int qcnn_forward_u8_relaxed_views_strided(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcPixels* imgs_host, int n,
                                           int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host,
                                           int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
-  return relaxed_views(c, "qcnn_forward_u8_relaxed_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev,
+  return u8_views<RelaxedMode>(c, "qcnn_forward_u8_relaxed_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev,
                        views_host, n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
@@ -2111,6 +2203,167 @@ int qcnn_forward_host_batches(QcnnCtx* c, const float* const* in_host, const int
     }
     for (hipEvent_t e : dbgEv) (void)hipEventDestroy(e);
   }
+  return 0;
+}
+
+namespace {
+// qcnn_forward_u8_resized_host_batches (Mode = StrictMode) and qcnn_forward_u8_relaxed_host_batches (RelaxedMode): the image
+// loop of src/CaffeEva.cc:151-211 with BmpImgIO::Load's work on the device and CalcPredAccu's counting (:263-295) behind every
+// labelled batch.  The schedule is qcnn_forward_host_batches', with 8-bit source bytes in place of float crops: the source
+// bytes and labels of batch b + 1 go up on the copy stream under the layers of batch b, into the buffer the pack kernel of
+// batch b - 1 has handed back; results return through the pinned pairs one batch late.
+extern "C++" template <class Mode>
+int u8_host_batches(QcnnCtx* c, const char* fn, const QcnnU8Batch* batches, int nb, int full_h, int full_w, const float* mean_dev,
+                    const typename Mode::View* views_host, int n_views, unsigned long long* hits5) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->committed) return fail(c, "model not committed");
+  if (nb <= 0 || !batches) return fail(c, "%s: no batches", fn);
+  if (!views_host) return fail(c, "%s: views == NULL", fn);
+  if (n_views < 1 || n_views > QCNN_MAX_VIEWS) return fail(c, "%d views outside [1, %d]", n_views, QCNN_MAX_VIEWS);
+  if (full_image_ok(c, full_h, full_w)) return 1;
+  typename Mode::Views views = {};
+  if (Mode::views(c, views_host, n_views, full_h, full_w, &views)) return 1;
+  // every batch is checked before anything is enqueued or any buffer rewritten
+  const unsigned classes = (unsigned)fm_elems(c, c->L);
+  size_t maxBytes = 0;
+  int maxN = 0;
+  bool anyMean = false;
+  for (int b = 0; b < nb; ++b) {
+    const QcnnU8Batch& q = batches[b];
+    if (!q.src_host || !q.imgs) return fail(c, "batch %d: src_host or imgs == NULL", b);
+    if (q.n <= 0) return fail(c, "batch %d: no image (n = %d)", b, q.n);
+    if ((long long)q.n * n_views > c->maxBatch)
+      return fail(c, "batch %d: %d images x %d views = %lld batch slots, the model is committed for %d", b, q.n, n_views,
+                  (long long)q.n * n_views, c->maxBatch);
+    for (int i = 0; i < q.n; ++i)
+      if (Mode::image(c, i, q.imgs[i], q.src_bytes, full_h, full_w, views, n_views)) {
+        c->err = "batch " + std::to_string(b) + ": " + c->err;
+        return 1;
+      }
+    for (int i = 0; q.labels && i < q.n; ++i)
+      if (q.labels[i] >= classes) return fail(c, "batch %d: image %d: label %u is no class of the model's %u", b, i, (unsigned)q.labels[i], classes);
+    maxBytes = std::max(maxBytes, q.src_bytes);
+    maxN = std::max(maxN, q.n);
+    anyMean = anyMean || q.prob_host || q.top5_host || (q.labels && hits5);
+  }
+  // everything that grows grows here: source buffers, the view-mean map, both descriptor staging sets (two takes: each set once)
+  if (ensure_u8_stream(c, maxBytes) || views_scratch(c, maxN, anyMean)) return 1;
+  using D = decltype(Mode::desc(batches[0].imgs[0], full_h, full_w));
+  for (int k = 0; k < 2; ++k)
+    if (!stage_take(c, (size_t)maxN, sizeof(D))) return 1;
+  QcnnCtx::U8Stream& s = c->u8s;
+  // the copy stream may not touch a source or label buffer before everything already enqueued on the compute stream has read it
+  for (int k = 0; k < 2; ++k) { HIP_TRY(c, hipEventRecord(c->evFreed[k], c->stream)); c->freedValid[k] = true; }
+  HIP_TRY(c, hipMemsetAsync(s.hits, 0, 5 * sizeof(unsigned long long), c->stream));
+  // QCNN_DEBUG_PIPELINE=1: time every upload and every batch's kernels with events and print the schedule afterwards
+  static const bool dbg = [] { const char* e = getenv("QCNN_DEBUG_PIPELINE"); return e && atoi(e) != 0; }();
+  std::vector<hipEvent_t> dbgEv;
+  bool counted[2] = {false, false};
+  auto run = [&]() -> int {
+    if (dbg) {
+      dbgEv.resize((size_t)nb * 4 + 1);
+      for (hipEvent_t& e : dbgEv) HIP_TRY(c, hipEventCreate(&e));
+      HIP_TRY(c, hipEventRecord(dbgEv[(size_t)nb * 4], c->stream));
+    }
+    auto upload = [&](int b) -> int {
+      const int k = b & 1;
+      const QcnnU8Batch& q = batches[b];
+      if (q.labels && hits5) {                          // through the pinned pair: the copy of batch b - 2 out of it has passed
+        if (b >= 2) HIP_TRY(c, hipEventSynchronize(c->evCopied[k]));
+        memcpy(s.pinLabels[k], q.labels, (size_t)q.n * sizeof(uint16_t));
+      }
+      HIP_TRY(c, hipStreamWaitEvent(c->copyStream, c->evFreed[k], 0));
+      if (dbg) HIP_TRY(c, hipEventRecord(dbgEv[(size_t)b * 4], c->copyStream));
+      HIP_TRY(c, hipMemcpyAsync(s.src[k], q.src_host, q.src_bytes, hipMemcpyHostToDevice, c->copyStream));
+      if (q.labels && hits5) {                          // labels[k]'s last reader is the hit count of batch b - 2, far behind its pack kernel
+        if (counted[k]) HIP_TRY(c, hipStreamWaitEvent(c->copyStream, s.evCounted[k], 0));
+        HIP_TRY(c, hipMemcpyAsync(s.labels[k], s.pinLabels[k], (size_t)q.n * sizeof(uint16_t), hipMemcpyHostToDevice, c->copyStream));
+      }
+      if (dbg) HIP_TRY(c, hipEventRecord(dbgEv[(size_t)b * 4 + 1], c->copyStream));
+      HIP_TRY(c, hipEventRecord(c->evCopied[k], c->copyStream));
+      return 0;
+    };
+    auto collect = [&](int b) -> int {
+      const int k = b & 1;
+      const QcnnU8Batch& q = batches[b];
+      HIP_TRY(c, hipEventSynchronize(c->evDone[k]));
+      if (q.prob_host) memcpy(q.prob_host, c->pinProb[k], (size_t)q.n * classes * sizeof(float));
+      if (q.top5_host) memcpy(q.top5_host, c->pinTop5[k], (size_t)q.n * 5 * sizeof(uint16_t));
+      if (q.prob_views_host) memcpy(q.prob_views_host, s.pinRows[k], (size_t)q.n * n_views * classes * sizeof(float));
+      return 0;
+    };
+    if (upload(0)) return 1;
+    for (int b = 0; b < nb; ++b) {
+      const int k = b & 1;
+      const QcnnU8Batch& q = batches[b];
+      if (b + 1 < nb && upload(b + 1)) return 1;
+      const bool count = q.labels && hits5;
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evCopied[k], 0));
+      if (dbg) HIP_TRY(c, hipEventRecord(dbgEv[(size_t)b * 4 + 2], c->stream));
+      if (u8_enqueue<Mode>(c, s.src[k], q.imgs, q.n, full_h, full_w, mean_dev, views, n_views, q.prob_host ? s.prob : nullptr,
+                           q.top5_host || count ? s.top5 : nullptr, q.prob_views_host ? s.rows : nullptr, c->evFreed[k]))
+        return 1;
+      if (count) {                                      // on the view-averaged rows: n labels, not n * n_views
+        const hipError_t e = qk_top5_hits(s.top5, s.labels[k], q.n, s.hits, c->stream);
+        if (e != hipSuccess) return fail(c, "hit count launch failed: %s", hipGetErrorString(e));
+        HIP_TRY(c, hipEventRecord(s.evCounted[k], c->stream));
+        counted[k] = true;
+      }
+      if (dbg) HIP_TRY(c, hipEventRecord(dbgEv[(size_t)b * 4 + 3], c->stream));
+      if (q.prob_host)
+        HIP_TRY(c, hipMemcpyAsync(c->pinProb[k], s.prob, (size_t)q.n * classes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      if (q.top5_host)
+        HIP_TRY(c, hipMemcpyAsync(c->pinTop5[k], s.top5, (size_t)q.n * 5 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+      if (q.prob_views_host)
+        HIP_TRY(c, hipMemcpyAsync(s.pinRows[k], s.rows, (size_t)q.n * n_views * classes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipEventRecord(c->evDone[k], c->stream));
+      if (b >= 1 && collect(b - 1)) return 1;
+    }
+    if (hits5) HIP_TRY(c, hipMemcpyAsync(s.pinHits, s.hits, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (collect(nb - 1)) return 1;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // the five counters: read back once
+    HIP_TRY(c, hipStreamSynchronize(c->copyStream));
+    return 0;
+  };
+  if (run()) {                                          // the caller's memory is not read behind a failed call's return
+    (void)hipStreamSynchronize(c->copyStream);
+    (void)hipStreamSynchronize(c->stream);
+    for (hipEvent_t e : dbgEv) if (e) (void)hipEventDestroy(e);
+    return 1;
+  }
+  if (hits5) memcpy(hits5, s.pinHits, 5 * sizeof(unsigned long long));
+  if (dbg) {
+    for (int b = 0; b < nb; ++b) {
+      float t[4];
+      for (int j = 0; j < 4; ++j) HIP_TRY(c, hipEventElapsedTime(&t[j], dbgEv[(size_t)nb * 4], dbgEv[(size_t)b * 4 + j]));
+      fprintf(stderr, "[qcnn pipeline] batch %d (%d images): upload %.2f -> %.2f ms, layers %.2f -> %.2f ms\n", b, batches[b].n, t[0],
+              t[1], t[2], t[3]);
+    }
+    for (hipEvent_t e : dbgEv) (void)hipEventDestroy(e);
+  }
+  return 0;
+}
+}  // namespace
+
+int qcnn_forward_u8_resized_host_batches(QcnnCtx* c, const QcnnU8Batch* batches, int nb, int full_h, int full_w, const float* mean_dev,
+                                         const QcnnView* views_host, int n_views, unsigned long long* hits5) {
+  return u8_host_batches<StrictMode>(c, "qcnn_forward_u8_resized_host_batches", batches, nb, full_h, full_w, mean_dev, views_host, n_views,
+                                     hits5);
+}
+
+int qcnn_forward_u8_relaxed_host_batches(QcnnCtx* c, const QcnnU8Batch* batches, int nb, int full_h, int full_w,
+                                         const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
+                                         unsigned long long* hits5) {
+  return u8_host_batches<RelaxedMode>(c, "qcnn_forward_u8_relaxed_host_batches", batches, nb, full_h, full_w, mean_crop_dev, views_host,
+                                      n_views, hits5);
+}
+
+int qcnn_count_top5_hits(QcnnCtx* c, const uint16_t* top5_dev, const uint16_t* labels_dev, int n, unsigned long long* hits5_dev) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!top5_dev || !labels_dev || !hits5_dev) return fail(c, "qcnn_count_top5_hits: top5, labels or hits5 == NULL");
+  if (n <= 0) return fail(c, "qcnn_count_top5_hits: no image (n = %d)", n);
+  const hipError_t e = qk_top5_hits(top5_dev, labels_dev, n, hits5_dev, c->stream);
+  if (e != hipSuccess) return fail(c, "hit count launch failed: %s", hipGetErrorString(e));
   return 0;
 }
 

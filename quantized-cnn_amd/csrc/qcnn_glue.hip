@@ -482,6 +482,32 @@ __global__ void k_top5(const float* __restrict__ prob, uint16_t* __restrict__ ou
   }
 }
 
+// CaffeEva::CalcPredAccu (src/CaffeEva.cc:276-286) before its running sum: hits[r] += #{ i : top5[i][r] == labels[i] }.  Every
+// rank is tested by itself: a row that repeats a class counts it at every rank where it stands.  One thread = one image; per
+// rank one ballot per wave, the waves' counts meet in LDS, and threads 0..4 add the workgroup's five sums: one 64-bit integer
+// atomic per workgroup and rank (integer sums do not depend on the order of arrival).  No lane leaves before the ballots: a
+// lane behind the last image votes "no" and reads nothing.
+constexpr int HITS_BLOCK = 256;
+__global__ __launch_bounds__(HITS_BLOCK) void k_top5_hits(const uint16_t* __restrict__ top5, const uint16_t* __restrict__ labels, int n,
+                                                          unsigned long long* __restrict__ hits) {
+  __shared__ unsigned cnt[HITS_BLOCK / 64][5];
+  const int i = blockIdx.x * HITS_BLOCK + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool live = i < n;
+  const unsigned label = live ? labels[i] : 0u;
+#pragma unroll
+  for (int r = 0; r < 5; ++r) {
+    const bool hit = live && top5[(size_t)i * 5 + r] == label;
+    const unsigned long long votes = __ballot(hit);
+    if (lane == 0) cnt[wave][r] = (unsigned)__popcll(votes);
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    unsigned sum = 0;
+    for (int w = 0; w < HITS_BLOCK / 64; ++w) sum += cnt[w][threadIdx.x];
+    if (sum) atomicAdd(&hits[threadIdx.x], (unsigned long long)sum);
+  }
+}
+
 // ---- the pack kernels: rows or 8-bit images -> panels [E][128] through a 128-slot x 64-element LDS tile (both sides
 // coalesced).  One block = 64 elements of one panel; wave w fills tile rows w, w + 4, ...; the shared pieces first. ----
 // The tile's write-out: element e0 + j of all 128 slots goes to panel row rowOf(e0 + j), two slots a lane.  rowOf is called
@@ -1000,6 +1026,12 @@ hipError_t qk_top5(const float* prob, uint16_t* out, int n, int C, hipStream_t s
     return hipGetLastError();
   }
   hipLaunchKernelGGL(k_top5, dim3((n + 63) / 64), dim3(64), 0, st, prob, out, n, C);
+  return hipGetLastError();
+}
+
+hipError_t qk_top5_hits(const uint16_t* top5, const uint16_t* labels, int n, unsigned long long* hits5, hipStream_t st) {
+  if (n <= 0 || !top5 || !labels || !hits5) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_top5_hits, dim3((n + HITS_BLOCK - 1) / HITS_BLOCK), dim3(HITS_BLOCK), 0, st, top5, labels, n, hits5);
   return hipGetLastError();
 }
 

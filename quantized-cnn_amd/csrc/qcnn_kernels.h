@@ -420,6 +420,8 @@ int qk_fc_dec_slices(int D, int Ct, int panels, int live);
 hipError_t qk_fc_dec(const FcDecParams& p, int slices, int live, hipStream_t st);   // slices > 1: add with qk_sum_partials
 hipError_t qk_softmax(const float* src, float* dst, int panels, int C, int live, hipStream_t st);
 hipError_t qk_top5(const float* prob, uint16_t* out, int n, int C, hipStream_t st);   // prob panel layout -> [n][5]
+// hits5[r] += number of images i < n with top5[i][r] == labels[i], every rank by itself (CalcPredAccu before its running sum)
+hipError_t qk_top5_hits(const uint16_t* top5, const uint16_t* labels, int n, unsigned long long* hits5, hipStream_t st);
 
 // [n][C][H][W] -> panels [H*W*C][128] (lanes >= n zero-filled)
 hipError_t qk_pack_nchw(const float* in, float* dst, int n, int C, int H, int W, hipStream_t st);

@@ -414,6 +414,98 @@ class QcnnEngine:
         overlapped with the layers of batch b (qcnn_forward_host_batches).  Returns ([prob_b], [top5_b])."""
         return _host_batches(self.lib.qcnn_forward_host_batches, self, batches, self.fm_dims(self.L), want_prob, want_top5)
 
+    def forward_u8_host_batches_into(self, batches, full_hw, mean_ptr, views, mode, outs, labels=None, hits5=None):
+        """The streamed 8-bit call on the caller's arrays (qcnn_forward_u8_resized_host_batches for mode "strict",
+        qcnn_forward_u8_relaxed_host_batches for "relaxed"); blocking.  batches: [(flat, descs)] — a one-dimensional uint8
+        array in host memory of any kind and the SrcPixels of the images in it; mean_ptr: a DEVICE pointer or None; outs: per
+        batch (prob, top5, prob_views), each a C-contiguous numpy array that is written or None; labels: per batch a uint16
+        array of one class per image or None (batch not counted), or None altogether; hits5: a uint64 array [5] that receives
+        the per-rank hit counts, or None (nothing is counted).  A refused call leaves every array as it was."""
+        if mode not in ("strict", "relaxed"):
+            raise ValueError("mode is 'strict' or 'relaxed'")
+        nb = len(batches)
+        if len(outs) != nb or (labels is not None and len(labels) != nb):
+            raise ValueError("outs and labels hold one entry per batch")
+        arr = (capi.QcnnU8Batch * max(nb, 1))()
+        keep = []                                     # the descriptor arrays and label copies live as long as the call
+        addr = lambda a: a.ctypes.data if a is not None else None
+        for b, ((flat, descs), (prob, top5, rows)) in enumerate(zip(batches, outs)):
+            if flat is not None and (not isinstance(flat, np.ndarray) or flat.dtype != np.uint8 or flat.ndim != 1 or not flat.flags["C_CONTIGUOUS"]):
+                raise ValueError("batch %d: the source buffer is a C-contiguous one-dimensional uint8 array" % b)
+            darr, n = _pixels_array(descs)
+            lab = labels[b] if labels is not None else None
+            if lab is not None:
+                lab = np.ascontiguousarray(lab, np.uint16)
+                if lab.shape != (n,):
+                    raise ValueError("batch %d: %d labels for %d images" % (b, lab.size, n))
+            keep.append((darr, lab))
+            arr[b] = capi.QcnnU8Batch(addr(flat), flat.size if flat is not None else 0, darr, n, addr(lab), addr(prob), addr(top5), addr(rows))
+        if hits5 is not None and (hits5.dtype != np.uint64 or hits5.shape != (5,) or not hits5.flags["C_CONTIGUOUS"]):
+            raise ValueError("hits5 is a uint64 array [5]")
+        hp = hits5.ctypes.data_as(C.POINTER(C.c_ulonglong)) if hits5 is not None else None
+        full_h, full_w = int(full_hw[0]), int(full_hw[1])
+        if mode == "strict":
+            varr, V = _struct_array(capi.QcnnView, views)
+            self._chk(self.lib.qcnn_forward_u8_resized_host_batches(self.h, arr, nb, full_h, full_w, _ptr(mean_ptr), varr, V, hp))
+        else:
+            varr, V = _struct_array(capi.QcnnAnchorView, views)
+            self._chk(self.lib.qcnn_forward_u8_relaxed_host_batches(self.h, arr, nb, full_h, full_w, _ptr(mean_ptr), varr, V, hp))
+
+    def forward_u8_host_batches(self, batches, full_hw, mean=None, views=None, mode="strict", labels=None, want=(True, True, False)):
+        """Blocking: batches of 8-bit source images streamed from host memory, the upload of batch b + 1 under the layers of
+        batch b (qcnn_forward_u8_*_host_batches).  batches: [(flat, descs)] as pack_bmp_files / pack_interleaved / pack_sources
+        + src_planar give them; full_hw, views and mean (float32 [C][full_h][full_w], "relaxed": [C][in_h][in_w]; or None) as
+        forward_u8_resized_host / forward_u8_relaxed_host take them (default view: the centre); labels: per batch one class per
+        image or None.  want = (prob, top5, prob_views).  Returns ([prob_b], [top5_b], [prob_views_b], hits5): per batch prob
+        [n][classes] and top5 [n][5] of the view average and prob_views [n][len(views)][classes] — a list that is not wanted is
+        None — and hits5, uint64 [5], or None without labels: hits5[r] = labelled images whose r-th prediction is their label,
+        every rank by itself (CaffeEva::CalcPredAccu before its running sum; ACCURACY@k is hits5[:k].sum() over the labelled
+        images: evaluate_u8).  numpy in, numpy out; torch only holds the mean on the device."""
+        full_h, full_w = int(full_hw[0]), int(full_hw[1])
+        _, in_h, in_w = self.in_chw
+        if views is None:
+            views = [((full_h - in_h) // 2, (full_w - in_w) // 2, 0)] if mode == "strict" else [(1, 1, 0, 0, 0)]
+        V = len(views)
+        fh, fw, fc = self.fm_dims(self.L)
+        classes = fh * fw * fc
+        d_mean = None
+        if mean is not None:
+            import torch   # plumbing only: the mean on the device
+            shape = (self.in_chw[0], full_h, full_w) if mode == "strict" else tuple(self.in_chw)
+            m = np.ascontiguousarray(mean, np.float32)
+            if m.shape != shape:
+                raise QcnnError("mean %r, expected %r" % (m.shape, shape))
+            dev = torch.device("cuda", self.lib.qcnn_ctx_device(self.h))
+            d_mean = torch.from_numpy(m).to(dev)
+            torch.cuda.synchronize(dev)
+        outs = [(np.empty((len(d), classes), np.float32) if want[0] else None, np.empty((len(d), 5), np.uint16) if want[1] else None,
+                 np.empty((len(d), V, classes), np.float32) if want[2] else None) for _, d in batches]
+        hits5 = np.zeros(5, np.uint64) if labels is not None else None
+        self.forward_u8_host_batches_into(batches, full_hw, d_mean.data_ptr() if d_mean is not None else None, views, mode, outs,
+                                          labels, hits5)
+        col = lambda j: [o[j] for o in outs] if want[j] else None
+        return col(0), col(1), col(2), hits5
+
+    def count_top5_hits_dev(self, top5_ptr: int, labels_ptr: int, n: int, hits_ptr: int):
+        """Asynchronous, device pointers (qcnn_count_top5_hits): hits[r] += images i < n whose r-th top-5 entry is labels[i],
+        every rank by itself — accumulated into the five uint64 counters at hits_ptr, which the caller zeroes."""
+        self._chk(self.lib.qcnn_count_top5_hits(self.h, _ptr(top5_ptr), _ptr(labels_ptr), n, _ptr(hits_ptr)))
+
+    def evaluate_u8(self, sources, labels, full_hw, mean, views=None, mode="strict", batch_images=None):
+        """Classify a labelled set of source images — what the reference's Main.cc does with its image files: split_batches +
+        forward_u8_host_batches.  sources / labels as split_batches takes them; batch_images: images per batch (default and
+        cap: max_batch // len(views)).  Returns dict(n, hits = the five per-rank counts, accuracy = the five CUMULATIVE
+        fractions hits[:k + 1].sum() / n: the numbers Main.cc prints as ACCURACY@1..5)."""
+        V = 1 if views is None else len(views)
+        per = self.max_batch // max(V, 1)
+        if batch_images is not None:
+            per = min(per, int(batch_images))
+        cut = split_batches(sources, labels, per * V, V)
+        _, _, _, hits = self.forward_u8_host_batches([(f, d) for f, d, _ in cut], full_hw, mean, views, mode, [l for _, _, l in cut],
+                                                     want=(False, False, False))
+        n = sum(len(d) for _, d, _ in cut)
+        return dict(n=n, hits=[int(h) for h in hits], accuracy=[float(int(hits[:k + 1].sum()) / n) for k in range(5)])
+
     def layer_output(self, l: int, n: int):
         h, w, c = self.fm_dims(l)
         out = np.empty((n, h, w, c), np.float32)
@@ -589,6 +681,55 @@ def pack_interleaved(images, order="BGR"):
     for a, d in zip(imgs, descs):
         flat[d.offset:d.offset + a.size] = a.reshape(-1)
     return flat, descs
+
+
+def split_batches(sources, labels, max_batch, n_views):
+    """Cut a list of per-image sources and their labels into the batches forward_u8_host_batches streams: every batch holds at
+    most max_batch // n_views images (n * n_views <= max_batch), the order is kept, the last batch may be ragged.  sources:
+    BMP files' contents (bytes: packed by pack_bmp_files and read in place) or uint8 arrays [C][h][w] (pack_sources +
+    src_planar), one kind per call; labels: one class per image, or None.  Returns [(flat, descs, labels_b)], labels_b a
+    uint16 array or None.  Pure Python: needs no device and pins nothing."""
+    srcs = list(sources)
+    if not srcs:
+        raise ValueError("split_batches: no image")
+    per = int(max_batch) // int(n_views) if int(n_views) >= 1 else 0
+    if per < 1:
+        raise ValueError("split_batches: max_batch %d holds no image of %d views" % (max_batch, n_views))
+    lab = None
+    if labels is not None:
+        lab = np.asarray(labels)
+        if lab.shape != (len(srcs),) or lab.dtype.kind not in "iu" or (lab.size and (lab.min() < 0 or lab.max() > 0xFFFF)):
+            raise ValueError("split_batches: labels are one class in [0, 65535] per image")
+        lab = lab.astype(np.uint16)
+    files = [isinstance(s, (bytes, bytearray, memoryview)) for s in srcs]
+    if any(files) and not all(files):
+        raise ValueError("split_batches: sources are BMP files' contents or uint8 arrays [C][h][w], not both")
+    out = []
+    for a in range(0, len(srcs), per):
+        part = srcs[a:a + per]
+        if files[0]:
+            flat, descs = pack_bmp_files(part)
+        else:
+            flat, planar = pack_sources(part)
+            descs = [_src_planar(off, h, w, int(part[0].shape[0])) for off, h, w in planar]
+        out.append((flat, descs, lab[a:a + per].copy() if lab is not None else None))
+    return out
+
+
+def host_alloc(nbytes: int):
+    """A uint8 array [nbytes] over pinned host memory of the HIP runtime (qcnn_host_alloc): the fastest source of an upload.
+    host_free(arr) releases it; the array must not be used afterwards."""
+    lib = capi.load()
+    p = C.c_void_p()
+    if lib.qcnn_host_alloc(int(nbytes), C.byref(p)):
+        raise QcnnError(lib.qcnn_last_error(None).decode())
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(int(nbytes),))
+
+
+def host_free(arr) -> None:
+    lib = capi.load()
+    if lib.qcnn_host_free(C.c_void_p(arr.ctypes.data)):
+        raise QcnnError(lib.qcnn_last_error(None).decode())
 
 
 def host_register(arr) -> None:
