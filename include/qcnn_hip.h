@@ -33,6 +33,9 @@
  *   qcnn_src_bmp + qcnn_forward_u8_resized_views_strided / _relaxed_views_strided
  *                               BmpImgIO::LoadBmpImg: the de-interleave, the flip and the row re-packing  src/BmpImgIO.cc:73-103
  *                               (the file's pixel array is read where it lies; so is a decoder's HWC output or a region of a frame)
+ *   qcnn_src_yuv_frame + qcnn_forward_u8_resized_views_yuv / _relaxed_views_yuv / qcnn_forward_u8_*_host_batches_yuv
+ *                               (no counterpart: the reference reads BMP only) YCbCr frames as decoders emit them — NV12, I420,
+ *                               4:4:4, YUY2 — converted to B, G, R in the taps of the resize, read where they lie
  *   qcnn_model_set_layer_dense  CaffePara::LoadLayerPara(false, ..) result src/CaffePara.cc:290-302
  *   / _set_layer_weights        -> CalcFeatMap_ConvPrec / _FCntPrec        src/CaffeEva.cc:681-758, 932-966
  *   qcnn_quantize_layer         produces what CaffePara::LoadLayerPara reads src/CaffePara.cc:262-288
@@ -446,6 +449,71 @@ int qcnn_forward_u8_relaxed_views_strided(QcnnCtx* ctx, const uint8_t* src_dev, 
                                           const float* mean_crop_dev /* [C][in_h][in_w] or NULL */,
                                           const QcnnAnchorView* views_host, int n_views,
                                           float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
+/* YCbCr frames read IN PLACE: what JPEG and video decoders emit — NV12 / NV21, I420 / YV12, 4:4:4 planes, packed YUY2 / UYVY —
+ * pitched, bottom-up or a region of a larger frame.  A frame is three sample planes over one source buffer; pixel (y, x) of the
+ * h x w image the network sees has the three bytes
+ *   Y  = src_dev[y_offset  + y * y_row_stride + x * y_pix_stride]
+ *   Cb = src_dev[cb_offset + (y >> sub_y) * c_row_stride + (x >> sub_x) * c_pix_stride]
+ *   Cr = src_dev[cr_offset + (y >> sub_y) * c_row_stride + (x >> sub_x) * c_pix_stride]
+ * Chroma is REPLICATED, never interpolated (the resize that follows is the interpolation); the chroma planes have
+ * ((h - 1) >> sub_y) + 1 rows and ((w - 1) >> sub_x) + 1 columns, so odd sizes are legal.  The pixel's network channels (0 = B,
+ * 1 = G, 2 = R) are 8-bit values from 32-bit signed integer arithmetic, >> an arithmetic shift (floor):
+ *   yy = (Y - y0) * ky;  cb = Cb - 128;  cr = Cr - 128
+ *   R = clamp255((yy + crv * cr + 32768) >> 16)
+ *   G = clamp255((yy - cbg * cb - crg * cr + 32768) >> 16)
+ *   B = clamp255((yy + cbu * cb + 32768) >> 16)
+ *   matrix            y0     ky     crv     cbg     crg     cbu
+ *   QCNN_YUV_JFIF      0  65536   91881   22554   46802  116130      full-range BT.601 (JPEG): Cb = Cr = 128 gives B = G = R = Y
+ *   QCNN_YUV_BT601    16  76309  104597   25675   53279  132201      limited range: 16 -> 0, 235 -> 255
+ *   QCNN_YUV_BT709    16  76309  117489   13975   34925  138438      limited range
+ * (no accumulator exceeds 3.6e7; every output lies within 1 of the rounded real-number formula).  Bytes that are no sample are
+ * never read; planes and frames may alias. */
+enum { QCNN_YUV_JFIF = 0, QCNN_YUV_BT601 = 1, QCNN_YUV_BT709 = 2 };   /* full-range BT.601 (JPEG); limited-range BT.601; limited-range BT.709 */
+typedef struct {
+  uint64_t y_offset, cb_offset, cr_offset;   /* byte, relative to the source buffer, of luma sample (0, 0) and of chroma samples (0, 0) */
+  int64_t  y_row_stride, c_row_stride;       /* bytes between rows of the luma plane / of both chroma planes; any sign, 0 legal */
+  int32_t  h, w;                             /* luma size = the image's size */
+  int32_t  y_pix_stride, c_pix_stride;       /* >= 1.  planar 1 / 1, NV12 1 / 2, YUY2 2 / 4 */
+  int32_t  sub_y, sub_x;                     /* 0 or 1: log2 of the chroma sub-sampling (4:4:4 = 0, 0; 4:2:2 = 0, 1; 4:2:0 = 1, 1) */
+  int32_t  matrix;                           /* QCNN_YUV_* */
+} QcnnSrcYuv;
+/* The descriptor of a frame in one of the common layouts whose first byte will lie at src_dev + frame_offset (host only: no
+ * device, no context).  pitch: bytes between luma rows, 0 = tight.
+ *   QCNN_YUV_NV12 / _NV21   h luma rows of `pitch` bytes, then ceil(h / 2) rows of interleaved Cb Cr / Cr Cb at the same pitch
+ *                           (tight: 2 * ceil(w / 2), the chroma row of an odd width is the longer one)
+ *   QCNN_YUV_I420 / _YV12   luma, then the Cb and Cr (YV12: Cr and Cb) planes of ceil(h / 2) rows at pitch (pitch + 1) / 2
+ *   QCNN_YUV_I444           three planes Y, Cb, Cr of `pitch`
+ *   QCNN_YUV_YUY2 / _UYVY   packed 4:2:2, Y0 Cb Y1 Cr / Cb Y0 Cr Y1: y_pix_stride 2, c_pix_stride 4 (tight: 4 * ceil(w / 2))
+ * Non-zero, nothing written: out NULL, an unknown format or matrix, h < 1 or w < 1, a pitch smaller than a row, a frame of
+ * 2^31 - 1 bytes or more, frame_offset + the frame beyond 64 bits. */
+enum { QCNN_YUV_NV12 = 0, QCNN_YUV_NV21 = 1, QCNN_YUV_I420 = 2, QCNN_YUV_YV12 = 3, QCNN_YUV_I444 = 4, QCNN_YUV_YUY2 = 5, QCNN_YUV_UYVY = 6 };
+int qcnn_src_yuv_frame(int format, uint64_t frame_offset, int h, int w, int64_t pitch, int matrix, QcnnSrcYuv* out);
+/* qcnn_forward_u8_resized_views_strided / qcnn_forward_u8_relaxed_views_strided on such frames: the 8-bit B, G, R values above
+ * are the four taps of the bilinear resize, and everything from there on is defined there — scales, weights, the division, the
+ * mean's position, mirroring, slot order, averaging, top-5, the three optional outputs, the staging of the host arrays,
+ * asynchrony.  A call returns, bit for bit, what the strided call returns on the planar B, G, R image the conversion makes of
+ * the frame.
+ * Checked before anything is enqueued (non-zero, a message naming the image and the plane — luma, Cb or Cr —, outputs
+ * untouched): everything the planar call checks — h, w >= 1 (Strict) or >= 2 (Relaxed) — and
+ *   a network whose input has not 3 channels;  y_pix_stride or c_pix_stride < 1;  sub_y or sub_x outside {0, 1};  an unknown matrix;
+ *   for each plane, in overflow-checked 64-bit arithmetic (an offset near 2^64 or a stride of INT64_MIN is refused, not wrapped),
+ *   with rows x cols = h x w (luma) or the chroma size above:
+ *     lowest byte touched   offset + min(0, (rows-1) * row_stride)                             below 0;
+ *     highest byte touched  offset + max(0, (rows-1) * row_stride) + (cols-1) * pix_stride     >= src_bytes
+ *                           (a layout whose last sample is byte src_bytes - 1 is accepted);
+ *   highest - lowest OVER ALL THREE PLANES >= 2^31 - 1  (the kernels keep every offset relative to luma sample (0, 0) in signed
+ *   32 bits).
+ * The row strides are otherwise free: 0 and values smaller than a row are legal if in bounds. */
+int qcnn_forward_u8_resized_views_yuv(QcnnCtx* ctx, const uint8_t* src_dev, size_t src_bytes,
+                                      const QcnnSrcYuv* imgs_host, int n, int full_h, int full_w,
+                                      const float* mean_dev /* [3][full_h][full_w] or NULL */,
+                                      const QcnnView* views_host, int n_views,
+                                      float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
+int qcnn_forward_u8_relaxed_views_yuv(QcnnCtx* ctx, const uint8_t* src_dev, size_t src_bytes,
+                                      const QcnnSrcYuv* imgs_host, int n, int full_h, int full_w,
+                                      const float* mean_crop_dev /* [3][in_h][in_w] or NULL */,
+                                      const QcnnAnchorView* views_host, int n_views,
+                                      float* prob_dev, uint16_t* top5_dev, float* prob_views_dev);
 /* Blocking convenience: host in, host out (H2D + forward + D2H + sync).  A batch of at least two chunks
  * (QCNN_OPT_HOST_CHUNK) goes through chunk by chunk, uploads overlapped with the previous chunk's layers. */
 int qcnn_forward_host(QcnnCtx* ctx, const float* in_nchw_host, int n, float* prob_host, uint16_t* top5_host);
@@ -494,6 +562,21 @@ int qcnn_forward_u8_resized_host_batches(QcnnCtx* ctx, const QcnnU8Batch* batche
 int qcnn_forward_u8_relaxed_host_batches(QcnnCtx* ctx, const QcnnU8Batch* batches, int nb, int full_h, int full_w,
                                          const float* mean_crop_dev /* [C][in_h][in_w] or NULL */,
                                          const QcnnAnchorView* views_host, int n_views, unsigned long long hits5[5] /* or NULL */);
+/* The same two calls for batches of YCbCr frames (qcnn_forward_u8_resized_views_yuv / _relaxed_views_yuv applied batch after
+ * batch): a 4:2:0 frame is 1.5 bytes a pixel where B, G, R are 3.  Schedule, buffers, labels, hits5, checks and messages
+ * ("batch 3: image 17: ...") are those above. */
+typedef struct QcnnU8YuvBatch {
+  const uint8_t* src_host; size_t src_bytes;   /* the batch's frames as they lie */
+  const QcnnSrcYuv* imgs; int n;               /* n descriptors, offsets relative to src_host */
+  const uint16_t* labels;                      /* n ground-truth classes, or NULL: batch not counted */
+  float* prob_host; uint16_t* top5_host; float* prob_views_host;   /* each may be NULL */
+} QcnnU8YuvBatch;
+int qcnn_forward_u8_resized_host_batches_yuv(QcnnCtx* ctx, const QcnnU8YuvBatch* batches, int nb, int full_h, int full_w,
+                                             const float* mean_dev /* [3][full_h][full_w] or NULL */,
+                                             const QcnnView* views_host, int n_views, unsigned long long hits5[5] /* or NULL */);
+int qcnn_forward_u8_relaxed_host_batches_yuv(QcnnCtx* ctx, const QcnnU8YuvBatch* batches, int nb, int full_h, int full_w,
+                                             const float* mean_crop_dev /* [3][in_h][in_w] or NULL */,
+                                             const QcnnAnchorView* views_host, int n_views, unsigned long long hits5[5] /* or NULL */);
 /* The counting alone, asynchronous on the context's stream, DEVICE pointers: hits5_dev[r] += #{ i < n : top5_dev[i * 5 + r] ==
  * labels_dev[i] } for r = 0..4 — accumulated INTO the five counters, which the caller zeroes.  Integer sums: the same from run
  * to run.  Non-zero for a NULL pointer or n <= 0. */

@@ -43,6 +43,18 @@ class QcnnSrcPixels(C.Structure):
                 ("pix_stride", C.c_int32), ("ch_offset", C.c_int32 * 4)]
 
 
+YUV_MATRICES = {"JFIF": 0, "BT601": 1, "BT709": 2}                                                 # QCNN_YUV_JFIF ...
+YUV_FORMATS = {"NV12": 0, "NV21": 1, "I420": 2, "YV12": 3, "I444": 4, "YUY2": 5, "UYVY": 6}       # QCNN_YUV_NV12 ...
+
+
+class QcnnSrcYuv(C.Structure):
+    """A YCbCr source frame of the _yuv calls, read in place: pixel (y, x) has Y at y_offset + y * y_row_stride + x * y_pix_stride
+    and Cb / Cr at cb_offset / cr_offset + (y >> sub_y) * c_row_stride + (x >> sub_x) * c_pix_stride of the source buffer."""
+    _fields_ = [("y_offset", C.c_uint64), ("cb_offset", C.c_uint64), ("cr_offset", C.c_uint64), ("y_row_stride", C.c_int64),
+                ("c_row_stride", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("y_pix_stride", C.c_int32),
+                ("c_pix_stride", C.c_int32), ("sub_y", C.c_int32), ("sub_x", C.c_int32), ("matrix", C.c_int32)]
+
+
 class QcnnAnchorView(C.Structure):
     """A view of qcnn_forward_u8_relaxed_views, placed relative to each image's own full size: anchor 0 / 1 / 2 = near edge /
     CropImg's centre / far edge on each axis, plus dy / dx pixels; flip: mirrored left-right."""
@@ -53,6 +65,12 @@ class QcnnU8Batch(C.Structure):
     """One batch of qcnn_forward_u8_*_host_batches: its source bytes in host memory as they lie, n descriptors with offsets
     relative to src_host, n labels or NULL (batch not counted), and the three host outputs, each of which may be NULL."""
     _fields_ = [("src_host", C.c_void_p), ("src_bytes", C.c_size_t), ("imgs", C.POINTER(QcnnSrcPixels)), ("n", C.c_int),
+                ("labels", C.c_void_p), ("prob_host", C.c_void_p), ("top5_host", C.c_void_p), ("prob_views_host", C.c_void_p)]
+
+
+class QcnnU8YuvBatch(C.Structure):
+    """QcnnU8Batch with YCbCr descriptors (qcnn_forward_u8_*_host_batches_yuv)."""
+    _fields_ = [("src_host", C.c_void_p), ("src_bytes", C.c_size_t), ("imgs", C.POINTER(QcnnSrcYuv)), ("n", C.c_int),
                 ("labels", C.c_void_p), ("prob_host", C.c_void_p), ("top5_host", C.c_void_p), ("prob_views_host", C.c_void_p)]
 
 
@@ -118,12 +136,21 @@ def load():
                                                           C.POINTER(QcnnView), i, f32p, u16p, f32p]
     lib.qcnn_forward_u8_relaxed_views_strided.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcPixels), i, i, i, f32p,
                                                           C.POINTER(QcnnAnchorView), i, f32p, u16p, f32p]
+    lib.qcnn_src_yuv_frame.argtypes = [i, C.c_uint64, i, i, C.c_int64, i, C.POINTER(QcnnSrcYuv)]
+    lib.qcnn_forward_u8_resized_views_yuv.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcYuv), i, i, i, f32p, C.POINTER(QcnnView), i,
+                                                      f32p, u16p, f32p]
+    lib.qcnn_forward_u8_relaxed_views_yuv.argtypes = [vp, u8p, C.c_size_t, C.POINTER(QcnnSrcYuv), i, i, i, f32p,
+                                                      C.POINTER(QcnnAnchorView), i, f32p, u16p, f32p]
     lib.qcnn_forward_host.argtypes = [vp, f32p, i, f32p, u16p]
     lib.qcnn_forward_host_batches.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, C.POINTER(vp), C.POINTER(vp)]
     lib.qcnn_forward_u8_resized_host_batches.argtypes = [vp, C.POINTER(QcnnU8Batch), i, i, i, f32p, C.POINTER(QcnnView), i,
                                                          C.POINTER(C.c_ulonglong)]
     lib.qcnn_forward_u8_relaxed_host_batches.argtypes = [vp, C.POINTER(QcnnU8Batch), i, i, i, f32p, C.POINTER(QcnnAnchorView), i,
                                                          C.POINTER(C.c_ulonglong)]
+    lib.qcnn_forward_u8_resized_host_batches_yuv.argtypes = [vp, C.POINTER(QcnnU8YuvBatch), i, i, i, f32p, C.POINTER(QcnnView), i,
+                                                             C.POINTER(C.c_ulonglong)]
+    lib.qcnn_forward_u8_relaxed_host_batches_yuv.argtypes = [vp, C.POINTER(QcnnU8YuvBatch), i, i, i, f32p, C.POINTER(QcnnAnchorView), i,
+                                                             C.POINTER(C.c_ulonglong)]
     lib.qcnn_count_top5_hits.argtypes = [vp, u16p, u16p, i, vp]
     lib.qcnn_host_register.argtypes = [vp, C.c_size_t]
     lib.qcnn_host_unregister.argtypes = [vp]

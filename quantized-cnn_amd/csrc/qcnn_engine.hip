@@ -23,6 +23,7 @@
 #include "qcnn_kernels.h"
 #include "qcnn_planner.h"
 #include "qcnn_src_layout.h"
+#include "qcnn_src_yuv.h"
 
 namespace {
 
@@ -1897,6 +1898,21 @@ int src_pixels_ok(QcnnCtx* c, int i, const QcnnSrcPixels& s, size_t src_bytes, i
 QkLayout layout_of(const QcnnSrcPixels& s) {
   return QkLayout{(int)(uint32_t)(uint64_t)s.row_stride, s.pix_stride, s.ch_offset[0], s.ch_offset[1], s.ch_offset[2], s.ch_offset[3]};
 }
+// Source image i of a YCbCr call: the same for three sample planes (qcnn_src_yuv.h holds the rules).
+int src_yuv_ok(QcnnCtx* c, int i, const QcnnSrcYuv& s, size_t src_bytes, int minSide) {
+  char why[320];
+  if (qcnn_yuv::check_yuv(s, c->inC, src_bytes, minSide, why, sizeof(why))) return fail(c, "image %d: %s", i, why);
+  return 0;
+}
+// The layout of a checked descriptor as the kernels take it: the row strides' low 32 bits (they differ from them only where a
+// plane has one row), the chroma bases as deltas from the luma base (32-bit: every sample lies within 2^31 - 1 bytes of every
+// other) and the matrix's six integers.
+QkYuvLayout yuv_layout_of(const QcnnSrcYuv& s) {
+  const int32_t* m = qcnn_yuv::matrix_ints(s.matrix);
+  return QkYuvLayout{(int)(uint32_t)(uint64_t)s.y_row_stride, s.y_pix_stride, (int)(uint32_t)(uint64_t)s.c_row_stride, s.c_pix_stride,
+                     (int)(uint32_t)(s.cb_offset - s.y_offset), (int)(uint32_t)(s.cr_offset - s.y_offset), s.sub_y, s.sub_x,
+                     m[0], m[1], m[2], m[3], m[4], m[5]};
+}
 // Stage n descriptors D — fill(i) makes image i's — and launch the pack kernel that reads them.  Called when every argument
 // is good: nothing is taken or rewritten for a call that is refused.  The set is marked in flight only once nothing of the
 // host's can fail any more, and its event is recorded behind its one reader.  afterPack (or nullptr): a second event recorded
@@ -1930,12 +1946,18 @@ int qcnn_forward_u8_views(QcnnCtx* c, const uint8_t* in_u8_dev, int src_h, int s
 }
 
 namespace {
-// What the planar and the strided calls differ in, by the type of the caller's descriptor: its check, the image part of the
+// What the planar, the strided and the YCbCr calls differ in, by the type of the caller's descriptor: its check, the image part of the
 // staged descriptor, the staged descriptor itself and the pack launch.
 extern "C++" {                                      // overloads
 int src_ok(QcnnCtx* c, int i, const QcnnSrcImage& s, size_t src_bytes, int minSide) { return src_image_ok(c, i, s, src_bytes, minSide); }
 int src_ok(QcnnCtx* c, int i, const QcnnSrcPixels& s, size_t src_bytes, int minSide) { return src_pixels_ok(c, i, s, src_bytes, minSide); }
+int src_ok(QcnnCtx* c, int i, const QcnnSrcYuv& s, size_t src_bytes, int minSide) { return src_yuv_ok(c, i, s, src_bytes, minSide); }
+uint64_t base_of(const QcnnSrcImage& s) { return s.offset; }       // the byte a staged descriptor's offsets are relative to
+uint64_t base_of(const QcnnSrcPixels& s) { return s.offset; }
+uint64_t base_of(const QcnnSrcYuv& s) { return s.y_offset; }        // luma sample (0, 0)
 QkSrcImage staged(const QcnnSrcImage&, const QkSrcImage& img) { return img; }
+QkSrcYuv staged(const QcnnSrcYuv& s, const QkSrcImage& img) { return QkSrcYuv{img, yuv_layout_of(s)}; }
+QkRelaxedYuv staged(const QcnnSrcYuv& s, const QkRelaxedImage& img) { return QkRelaxedYuv{img, yuv_layout_of(s)}; }
 QkSrcPixels staged(const QcnnSrcPixels& s, const QkSrcImage& img) { return QkSrcPixels{img, layout_of(s)}; }
 QkRelaxedImage staged(const QcnnSrcImage&, const QkRelaxedImage& img) { return img; }
 QkRelaxedPixels staged(const QcnnSrcPixels& s, const QkRelaxedImage& img) { return QkRelaxedPixels{img, layout_of(s)}; }
@@ -1943,6 +1965,10 @@ hipError_t pack_resized(const uint8_t* in, const QkSrcImage* d, const float* mea
                         int H, int W, int Hf, int Wf, hipStream_t st) { return qk_pack_u8_resized(in, d, mean, dst, n, V, views, C, H, W, Hf, Wf, st); }
 hipError_t pack_resized(const uint8_t* in, const QkSrcPixels* d, const float* mean, float* dst, int n, int V, const QkViews& views, int C,
                         int H, int W, int Hf, int Wf, hipStream_t st) { return qk_pack_u8_resized_strided(in, d, mean, dst, n, V, views, C, H, W, Hf, Wf, st); }
+hipError_t pack_resized(const uint8_t* in, const QkSrcYuv* d, const float* mean, float* dst, int n, int V, const QkViews& views, int C,
+                        int H, int W, int Hf, int Wf, hipStream_t st) { return qk_pack_u8_resized_yuv(in, d, mean, dst, n, V, views, C, H, W, Hf, Wf, st); }
+hipError_t pack_relaxed(const uint8_t* in, const QkRelaxedYuv* d, const float* mean, float* dst, int n, int V, const QkAnchorViews& views,
+                        int C, int H, int W, hipStream_t st) { return qk_pack_u8_relaxed_yuv(in, d, mean, dst, n, V, views, C, H, W, st); }
 hipError_t pack_relaxed(const uint8_t* in, const QkRelaxedImage* d, const float* mean, float* dst, int n, int V, const QkAnchorViews& views,
                         int C, int H, int W, hipStream_t st) { return qk_pack_u8_relaxed(in, d, mean, dst, n, V, views, C, H, W, st); }
 hipError_t pack_relaxed(const uint8_t* in, const QkRelaxedPixels* d, const float* mean, float* dst, int n, int V, const QkAnchorViews& views,
@@ -1963,7 +1989,7 @@ struct StrictMode {
   template <class Src>
   static int image(QcnnCtx* c, int i, const Src& s, size_t src_bytes, int, int, const Views&, int) { return src_ok(c, i, s, src_bytes, 1); }
   template <class Src> static auto desc(const Src& s, int full_h, int full_w) {   // the scales: one IEEE division each, as ReszImg computes them
-    return staged(s, QkSrcImage{s.offset, s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)});
+    return staged(s, QkSrcImage{base_of(s), s.h, s.w, (float)(s.h - 1) / (float)(full_h - 1), (float)(s.w - 1) / (float)(full_w - 1)});
   }
   template <class D>
   static hipError_t pack(QcnnCtx* c, const uint8_t* src_dev, const D* d, const float* mean_dev, int n, int n_views, const Views& views,
@@ -1999,7 +2025,7 @@ struct RelaxedMode {
     return 0;
   }
   template <class Src> static auto desc(const Src& s, int full_h, int full_w) {   // each image's scale and full size
-    QkRelaxedImage d = {s.offset, s.h, s.w, 0.0f, 0, 0, 0};
+    QkRelaxedImage d = {base_of(s), s.h, s.w, 0.0f, 0, 0, 0};
     (void)qcnn_relaxed_full_size(s.h, s.w, full_h, full_w, &d.hf, &d.wf, &d.s);     // succeeded in image()
     return staged(s, d);
   }
@@ -2025,7 +2051,7 @@ int u8_enqueue(QcnnCtx* c, const uint8_t* src_dev, const Src* imgs_host, int n, 
 }
 
 // qcnn_forward_u8_resized_views[_strided] (Mode = StrictMode) and qcnn_forward_u8_relaxed_views[_strided] (RelaxedMode), for
-// planar (Src = QcnnSrcImage) and strided (QcnnSrcPixels) descriptors.
+// planar (Src = QcnnSrcImage), strided (QcnnSrcPixels) and YCbCr (QcnnSrcYuv) descriptors.
 template <class Mode, class Src>
 int u8_views(QcnnCtx* c, const char* fn, const uint8_t* src_dev, size_t src_bytes, const Src* imgs_host, int n, int full_h, int full_w,
              const float* mean_dev, const typename Mode::View* views_host, int n_views, float* prob_dev, uint16_t* top5_dev,
@@ -2054,6 +2080,17 @@ int qcnn_forward_u8_resized_views_strided(QcnnCtx* c, const uint8_t* src_dev, si
                                           float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
   return u8_views<StrictMode>(c, "qcnn_forward_u8_resized_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host,
                        n_views, prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_forward_u8_resized_views_yuv(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcYuv* imgs_host, int n, int full_h,
+                                      int full_w, const float* mean_dev, const QcnnView* views_host, int n_views, float* prob_dev,
+                                      uint16_t* top5_dev, float* prob_views_dev) {
+  return u8_views<StrictMode>(c, "qcnn_forward_u8_resized_views_yuv", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_dev, views_host,
+                       n_views, prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_src_yuv_frame(int format, uint64_t frame_offset, int h, int w, int64_t pitch, int matrix, QcnnSrcYuv* out) {
+  return qcnn_yuv::yuv_frame(format, frame_offset, h, w, pitch, matrix, out);
 }
 
 int qcnn_src_planar(const QcnnSrcImage* img, int C, QcnnSrcPixels* out) { return qcnn_src::planar_pixels(img, C, out); }
@@ -2094,6 +2131,13 @@ int qcnn_forward_u8_relaxed_views_strided(QcnnCtx* c, const uint8_t* src_dev, si
                                           int full_h, int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host,
                                           int n_views, float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
   return u8_views<RelaxedMode>(c, "qcnn_forward_u8_relaxed_views_strided", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev,
+                       views_host, n_views, prob_dev, top5_dev, prob_views_dev);
+}
+
+int qcnn_forward_u8_relaxed_views_yuv(QcnnCtx* c, const uint8_t* src_dev, size_t src_bytes, const QcnnSrcYuv* imgs_host, int n, int full_h,
+                                      int full_w, const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
+                                      float* prob_dev, uint16_t* top5_dev, float* prob_views_dev) {
+  return u8_views<RelaxedMode>(c, "qcnn_forward_u8_relaxed_views_yuv", src_dev, src_bytes, imgs_host, n, full_h, full_w, mean_crop_dev,
                        views_host, n_views, prob_dev, top5_dev, prob_views_dev);
 }
 
@@ -2212,8 +2256,8 @@ namespace {
 // labelled batch.  The schedule is qcnn_forward_host_batches', with 8-bit source bytes in place of float crops: the source
 // bytes and labels of batch b + 1 go up on the copy stream under the layers of batch b, into the buffer the pack kernel of
 // batch b - 1 has handed back; results return through the pinned pairs one batch late.
-extern "C++" template <class Mode>
-int u8_host_batches(QcnnCtx* c, const char* fn, const QcnnU8Batch* batches, int nb, int full_h, int full_w, const float* mean_dev,
+extern "C++" template <class Mode, class Batch>       // Batch: QcnnU8Batch (strided descriptors) or QcnnU8YuvBatch (YCbCr)
+int u8_host_batches(QcnnCtx* c, const char* fn, const Batch* batches, int nb, int full_h, int full_w, const float* mean_dev,
                     const typename Mode::View* views_host, int n_views, unsigned long long* hits5) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->committed) return fail(c, "model not committed");
@@ -2229,7 +2273,7 @@ int u8_host_batches(QcnnCtx* c, const char* fn, const QcnnU8Batch* batches, int 
   int maxN = 0;
   bool anyMean = false;
   for (int b = 0; b < nb; ++b) {
-    const QcnnU8Batch& q = batches[b];
+    const Batch& q = batches[b];
     if (!q.src_host || !q.imgs) return fail(c, "batch %d: src_host or imgs == NULL", b);
     if (q.n <= 0) return fail(c, "batch %d: no image (n = %d)", b, q.n);
     if ((long long)q.n * n_views > c->maxBatch)
@@ -2267,7 +2311,7 @@ int u8_host_batches(QcnnCtx* c, const char* fn, const QcnnU8Batch* batches, int 
     }
     auto upload = [&](int b) -> int {
       const int k = b & 1;
-      const QcnnU8Batch& q = batches[b];
+      const Batch& q = batches[b];
       if (q.labels && hits5) {                          // through the pinned pair: the copy of batch b - 2 out of it has passed
         if (b >= 2) HIP_TRY(c, hipEventSynchronize(c->evCopied[k]));
         memcpy(s.pinLabels[k], q.labels, (size_t)q.n * sizeof(uint16_t));
@@ -2285,7 +2329,7 @@ int u8_host_batches(QcnnCtx* c, const char* fn, const QcnnU8Batch* batches, int 
     };
     auto collect = [&](int b) -> int {
       const int k = b & 1;
-      const QcnnU8Batch& q = batches[b];
+      const Batch& q = batches[b];
       HIP_TRY(c, hipEventSynchronize(c->evDone[k]));
       if (q.prob_host) memcpy(q.prob_host, c->pinProb[k], (size_t)q.n * classes * sizeof(float));
       if (q.top5_host) memcpy(q.top5_host, c->pinTop5[k], (size_t)q.n * 5 * sizeof(uint16_t));
@@ -2295,7 +2339,7 @@ int u8_host_batches(QcnnCtx* c, const char* fn, const QcnnU8Batch* batches, int 
     if (upload(0)) return 1;
     for (int b = 0; b < nb; ++b) {
       const int k = b & 1;
-      const QcnnU8Batch& q = batches[b];
+      const Batch& q = batches[b];
       if (b + 1 < nb && upload(b + 1)) return 1;
       const bool count = q.labels && hits5;
       HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evCopied[k], 0));
@@ -2355,6 +2399,19 @@ int qcnn_forward_u8_relaxed_host_batches(QcnnCtx* c, const QcnnU8Batch* batches,
                                          const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
                                          unsigned long long* hits5) {
   return u8_host_batches<RelaxedMode>(c, "qcnn_forward_u8_relaxed_host_batches", batches, nb, full_h, full_w, mean_crop_dev, views_host,
+                                      n_views, hits5);
+}
+
+int qcnn_forward_u8_resized_host_batches_yuv(QcnnCtx* c, const QcnnU8YuvBatch* batches, int nb, int full_h, int full_w, const float* mean_dev,
+                                             const QcnnView* views_host, int n_views, unsigned long long* hits5) {
+  return u8_host_batches<StrictMode>(c, "qcnn_forward_u8_resized_host_batches_yuv", batches, nb, full_h, full_w, mean_dev, views_host,
+                                     n_views, hits5);
+}
+
+int qcnn_forward_u8_relaxed_host_batches_yuv(QcnnCtx* c, const QcnnU8YuvBatch* batches, int nb, int full_h, int full_w,
+                                             const float* mean_crop_dev, const QcnnAnchorView* views_host, int n_views,
+                                             unsigned long long* hits5) {
+  return u8_host_batches<RelaxedMode>(c, "qcnn_forward_u8_relaxed_host_batches_yuv", batches, nb, full_h, full_w, mean_crop_dev, views_host,
                                       n_views, hits5);
 }
 

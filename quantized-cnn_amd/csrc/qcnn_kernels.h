@@ -476,6 +476,19 @@ hipError_t qk_pack_u8_resized_strided(const uint8_t* in, const QkSrcPixels* desc
                                       const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st);
 hipError_t qk_pack_u8_relaxed_strided(const uint8_t* in, const QkRelaxedPixels* desc, const float* mean, float* dst, int n, int V,
                                       const QkAnchorViews& views, int C, int H, int W, hipStream_t st);
+// The YCbCr forms (qcnn_forward_u8_resized_views_yuv / _relaxed_views_yuv): the same descriptors with the layout of a QcnnSrcYuv
+// behind them.  img.off is the luma base, luma sample (0, 0); Y of pixel (y, x) is the byte at in + off + (int)(y * yrs + x * yps),
+// Cb the byte at in + off + (int)(dcb + (y >> sy) * crs + (x >> sx) * cps), Cr likewise from dcr — dcb / dcr are the chroma bases as
+// deltas from the luma base, and every sum is formed in 32 bits (exact modulo 2^32: the engine checked that every sample of all
+// three planes lies less than 2^31 - 1 bytes from every other; yrs / crs are the row strides' low 32 bits, which differ from them
+// only where the plane has one row).  y0 .. cbu: the six integers of the matrix (include/qcnn_hip.h).  C == 3.
+struct QkYuvLayout { int yrs, yps, crs, cps, dcb, dcr, sy, sx, y0, ky, crv, cbg, crg, cbu; };
+struct QkSrcYuv { QkSrcImage img; QkYuvLayout lay; };               // 80 bytes
+struct QkRelaxedYuv { QkRelaxedImage img; QkYuvLayout lay; };       // 88 bytes
+hipError_t qk_pack_u8_resized_yuv(const uint8_t* in, const QkSrcYuv* desc, const float* mean, float* dst, int n, int V,
+                                  const QkViews& views, int C, int H, int W, int Hf, int Wf, hipStream_t st);
+hipError_t qk_pack_u8_relaxed_yuv(const uint8_t* in, const QkRelaxedYuv* desc, const float* mean, float* dst, int n, int V,
+                                  const QkAnchorViews& views, int C, int H, int W, hipStream_t st);
 // panels [C][128] of n * V slots -> panels [C][128] of n images: the mean over the V slots of an image, summed in slot order
 // in fp32 and divided by (float)V (lanes >= n zero-filled)
 hipError_t qk_mean_views(const float* src, float* dst, int n, int V, int C, hipStream_t st);

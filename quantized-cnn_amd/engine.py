@@ -73,6 +73,39 @@ def _from_c(d):
     return SrcPixels(int(d.offset), int(d.row_stride), int(d.h), int(d.w), int(d.pix_stride), tuple(int(v) for v in d.ch_offset))
 
 
+class SrcYuv(collections.namedtuple("SrcYuv", "y_offset cb_offset cr_offset y_row_stride c_row_stride h w y_pix_stride c_pix_stride "
+                                             "sub_y sub_x matrix")):
+    """A YCbCr source frame of the _yuv calls as Python holds it (capi.QcnnSrcYuv): pixel (y, x) has Y at y_offset +
+    y * y_row_stride + x * y_pix_stride and Cb / Cr at cb_offset / cr_offset + (y >> sub_y) * c_row_stride + (x >> sub_x) *
+    c_pix_stride of the source buffer.  matrix: the integer of capi.YUV_MATRICES."""
+    __slots__ = ()
+
+    def sample_index(self):
+        """int64 [3][h][w]: the bytes of Y, Cb and Cr of every pixel in the source buffer (chroma replicated)."""
+        y = np.arange(self.h, dtype=np.int64)[:, None]
+        x = np.arange(self.w, dtype=np.int64)[None, :]
+        c = (y >> int(self.sub_y)) * int(self.c_row_stride) + (x >> int(self.sub_x)) * int(self.c_pix_stride)
+        return np.stack([int(self.y_offset) + y * int(self.y_row_stride) + x * int(self.y_pix_stride), int(self.cb_offset) + c,
+                         int(self.cr_offset) + c])
+
+
+def _yuv_array(descs):
+    """(ctypes array of QcnnSrcYuv, length) of SrcYuv rows."""
+    if isinstance(descs, C.Array) and descs._type_ is capi.QcnnSrcYuv:       # made once by the caller: no per-call conversion
+        return descs, len(descs)
+    return _struct_array(capi.QcnnSrcYuv, descs)
+
+
+def _is_yuv(descs):
+    """Are these the descriptors of YCbCr frames (SrcYuv / capi.QcnnSrcYuv) and not of strided pixels?  One kind per call."""
+    if isinstance(descs, C.Array):
+        return descs._type_ is capi.QcnnSrcYuv
+    kinds = {isinstance(d, SrcYuv) for d in descs}
+    if len(kinds) > 1:
+        raise ValueError("the descriptors of one call are SrcPixels or SrcYuv, not both")
+    return kinds == {True}
+
+
 class QcnnEngine:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load()
@@ -316,18 +349,42 @@ class QcnnEngine:
                                                                  _ptr(mean_ptr), varr, V, _ptr(prob_ptr), _ptr(top5_ptr),
                                                                  _ptr(prob_views_ptr)))
 
+    def forward_u8_resized_views_yuv_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int, mean_ptr: int | None,
+                                         views, prob_ptr: int | None = None, top5_ptr: int | None = None,
+                                         prob_views_ptr: int | None = None):
+        """forward_u8_resized_views_strided_dev on YCbCr frames read in place (qcnn_forward_u8_resized_views_yuv): bit for bit
+        what it returns on the planar B, G, R images the integer conversion makes of the frames.  descs: a sequence of SrcYuv
+        — src_yuv_frame and pack_yuv_frames make them — or a ready ctypes array of capi.QcnnSrcYuv."""
+        darr, n = _yuv_array(descs)
+        varr, V = _struct_array(capi.QcnnView, views)
+        self._chk(self.lib.qcnn_forward_u8_resized_views_yuv(self.h, _ptr(src_ptr), src_bytes, darr, n, full_h, full_w, _ptr(mean_ptr),
+                                                             varr, V, _ptr(prob_ptr), _ptr(top5_ptr), _ptr(prob_views_ptr)))
+
+    def forward_u8_relaxed_views_yuv_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int,
+                                         mean_crop_ptr: int | None, views, prob_ptr: int | None = None,
+                                         top5_ptr: int | None = None, prob_views_ptr: int | None = None):
+        """forward_u8_relaxed_views_strided_dev on YCbCr frames read in place (qcnn_forward_u8_relaxed_views_yuv); descs as
+        forward_u8_resized_views_yuv_dev takes them."""
+        darr, n = _yuv_array(descs)
+        varr, V = _struct_array(capi.QcnnAnchorView, views)
+        self._chk(self.lib.qcnn_forward_u8_relaxed_views_yuv(self.h, _ptr(src_ptr), src_bytes, darr, n, full_h, full_w,
+                                                             _ptr(mean_crop_ptr), varr, V, _ptr(prob_ptr), _ptr(top5_ptr),
+                                                             _ptr(prob_views_ptr)))
+
     def forward_u8_resized_host(self, images, full_hw, mean=None, views=None, descs=None):
         """Blocking convenience: images — a list of uint8 arrays [C][h][w] of differing sizes — are packed, uploaded, resized
         to full_hw = (full_h, full_w) on the device, the float32 mean [C][full_h][full_w] (or None) subtracted, and evaluated on
         `views` (default: the centre crop alone, which makes the call BmpImgIO::Load + the forward pass).  With images = None
         and descs = (flat, descs) — a uint8 buffer and the SrcPixels of the images in it, as pack_bmp_files / pack_interleaved
-        give them — the buffer is uploaded untouched and read in place.  Returns (prob [n][classes] averaged over the views,
+        give them, or the SrcYuv of YCbCr frames (pack_yuv_frames; one kind per call) — the buffer is uploaded untouched and read
+        in place.  Returns (prob [n][classes] averaged over the views,
         top5 [n][5], prob_views [n][len(views)][classes]) as numpy arrays."""
         full_h, full_w = int(full_hw[0]), int(full_hw[1])
         _, in_h, in_w = self.in_chw
         if views is None:
             views = [((full_h - in_h) // 2, (full_w - in_w) // 2, 0)]
-        call = self.forward_u8_resized_views_dev if descs is None else self.forward_u8_resized_views_strided_dev
+        call = (self.forward_u8_resized_views_dev if descs is None else
+                self.forward_u8_resized_views_yuv_dev if _is_yuv(list(descs[1])) else self.forward_u8_resized_views_strided_dev)
         return self._u8_host(call, images, full_h, full_w, mean, "mean image", (self.in_chw[0], full_h, full_w), views, descs)
 
     def forward_u8_relaxed_views_dev(self, src_ptr: int, src_bytes: int, descs, full_h: int, full_w: int, mean_crop_ptr: int | None,
@@ -365,7 +422,8 @@ class QcnnEngine:
         arrays."""
         if views is None:
             views = [(1, 1, 0, 0, 0)]
-        call = self.forward_u8_relaxed_views_dev if descs is None else self.forward_u8_relaxed_views_strided_dev
+        call = (self.forward_u8_relaxed_views_dev if descs is None else
+                self.forward_u8_relaxed_views_yuv_dev if _is_yuv(list(descs[1])) else self.forward_u8_relaxed_views_strided_dev)
         return self._u8_host(call, images, int(full_hw[0]), int(full_hw[1]), mean_crop, "crop mean", tuple(self.in_chw), views, descs)
 
     def _u8_host(self, call, images, full_h, full_w, mean, mean_name, mean_shape, views, given=None):
@@ -417,7 +475,8 @@ class QcnnEngine:
     def forward_u8_host_batches_into(self, batches, full_hw, mean_ptr, views, mode, outs, labels=None, hits5=None):
         """The streamed 8-bit call on the caller's arrays (qcnn_forward_u8_resized_host_batches for mode "strict",
         qcnn_forward_u8_relaxed_host_batches for "relaxed"); blocking.  batches: [(flat, descs)] — a one-dimensional uint8
-        array in host memory of any kind and the SrcPixels of the images in it; mean_ptr: a DEVICE pointer or None; outs: per
+        array in host memory of any kind and the SrcPixels of the images in it, or the SrcYuv of YCbCr frames (then the _yuv
+        entry points run; one kind per call); mean_ptr: a DEVICE pointer or None; outs: per
         batch (prob, top5, prob_views), each a C-contiguous numpy array that is written or None; labels: per batch a uint16
         array of one class per image or None (batch not counted), or None altogether; hits5: a uint64 array [5] that receives
         the per-rank hit counts, or None (nothing is counted).  A refused call leaves every array as it was."""
@@ -426,35 +485,40 @@ class QcnnEngine:
         nb = len(batches)
         if len(outs) != nb or (labels is not None and len(labels) != nb):
             raise ValueError("outs and labels hold one entry per batch")
-        arr = (capi.QcnnU8Batch * max(nb, 1))()
+        yuv = {_is_yuv(descs) for _, descs in batches}
+        if len(yuv) > 1:
+            raise ValueError("the descriptors of one call are SrcPixels or SrcYuv, not both")
+        yuv = yuv == {True}
+        batch_t, to_array, tag = (capi.QcnnU8YuvBatch, _yuv_array, "_yuv") if yuv else (capi.QcnnU8Batch, _pixels_array, "")
+        arr = (batch_t * max(nb, 1))()
         keep = []                                     # the descriptor arrays and label copies live as long as the call
         addr = lambda a: a.ctypes.data if a is not None else None
         for b, ((flat, descs), (prob, top5, rows)) in enumerate(zip(batches, outs)):
             if flat is not None and (not isinstance(flat, np.ndarray) or flat.dtype != np.uint8 or flat.ndim != 1 or not flat.flags["C_CONTIGUOUS"]):
                 raise ValueError("batch %d: the source buffer is a C-contiguous one-dimensional uint8 array" % b)
-            darr, n = _pixels_array(descs)
+            darr, n = to_array(descs)
             lab = labels[b] if labels is not None else None
             if lab is not None:
                 lab = np.ascontiguousarray(lab, np.uint16)
                 if lab.shape != (n,):
                     raise ValueError("batch %d: %d labels for %d images" % (b, lab.size, n))
             keep.append((darr, lab))
-            arr[b] = capi.QcnnU8Batch(addr(flat), flat.size if flat is not None else 0, darr, n, addr(lab), addr(prob), addr(top5), addr(rows))
+            arr[b] = batch_t(addr(flat), flat.size if flat is not None else 0, darr, n, addr(lab), addr(prob), addr(top5), addr(rows))
         if hits5 is not None and (hits5.dtype != np.uint64 or hits5.shape != (5,) or not hits5.flags["C_CONTIGUOUS"]):
             raise ValueError("hits5 is a uint64 array [5]")
         hp = hits5.ctypes.data_as(C.POINTER(C.c_ulonglong)) if hits5 is not None else None
         full_h, full_w = int(full_hw[0]), int(full_hw[1])
         if mode == "strict":
             varr, V = _struct_array(capi.QcnnView, views)
-            self._chk(self.lib.qcnn_forward_u8_resized_host_batches(self.h, arr, nb, full_h, full_w, _ptr(mean_ptr), varr, V, hp))
+            self._chk(getattr(self.lib, "qcnn_forward_u8_resized_host_batches" + tag)(self.h, arr, nb, full_h, full_w, _ptr(mean_ptr), varr, V, hp))
         else:
             varr, V = _struct_array(capi.QcnnAnchorView, views)
-            self._chk(self.lib.qcnn_forward_u8_relaxed_host_batches(self.h, arr, nb, full_h, full_w, _ptr(mean_ptr), varr, V, hp))
+            self._chk(getattr(self.lib, "qcnn_forward_u8_relaxed_host_batches" + tag)(self.h, arr, nb, full_h, full_w, _ptr(mean_ptr), varr, V, hp))
 
     def forward_u8_host_batches(self, batches, full_hw, mean=None, views=None, mode="strict", labels=None, want=(True, True, False)):
         """Blocking: batches of 8-bit source images streamed from host memory, the upload of batch b + 1 under the layers of
         batch b (qcnn_forward_u8_*_host_batches).  batches: [(flat, descs)] as pack_bmp_files / pack_interleaved / pack_sources
-        + src_planar give them; full_hw, views and mean (float32 [C][full_h][full_w], "relaxed": [C][in_h][in_w]; or None) as
+        + src_planar or pack_yuv_frames give them; full_hw, views and mean (float32 [C][full_h][full_w], "relaxed": [C][in_h][in_w]; or None) as
         forward_u8_resized_host / forward_u8_relaxed_host take them (default view: the centre); labels: per batch one class per
         image or None.  want = (prob, top5, prob_views).  Returns ([prob_b], [top5_b], [prob_views_b], hits5): per batch prob
         [n][classes] and top5 [n][5] of the view average and prob_views [n][len(views)][classes] — a list that is not wanted is
@@ -491,16 +555,16 @@ class QcnnEngine:
         every rank by itself — accumulated into the five uint64 counters at hits_ptr, which the caller zeroes."""
         self._chk(self.lib.qcnn_count_top5_hits(self.h, _ptr(top5_ptr), _ptr(labels_ptr), n, _ptr(hits_ptr)))
 
-    def evaluate_u8(self, sources, labels, full_hw, mean, views=None, mode="strict", batch_images=None):
+    def evaluate_u8(self, sources, labels, full_hw, mean, views=None, mode="strict", batch_images=None, yuv=None):
         """Classify a labelled set of source images — what the reference's Main.cc does with its image files: split_batches +
-        forward_u8_host_batches.  sources / labels as split_batches takes them; batch_images: images per batch (default and
+        forward_u8_host_batches.  sources / labels / yuv as split_batches takes them; batch_images: images per batch (default and
         cap: max_batch // len(views)).  Returns dict(n, hits = the five per-rank counts, accuracy = the five CUMULATIVE
         fractions hits[:k + 1].sum() / n: the numbers Main.cc prints as ACCURACY@1..5)."""
         V = 1 if views is None else len(views)
         per = self.max_batch // max(V, 1)
         if batch_images is not None:
             per = min(per, int(batch_images))
-        cut = split_batches(sources, labels, per * V, V)
+        cut = split_batches(sources, labels, per * V, V, yuv)
         _, _, _, hits = self.forward_u8_host_batches([(f, d) for f, d, _ in cut], full_hw, mean, views, mode, [l for _, _, l in cut],
                                                      want=(False, False, False))
         n = sum(len(d) for _, d, _ in cut)
@@ -683,11 +747,47 @@ def pack_interleaved(images, order="BGR"):
     return flat, descs
 
 
-def split_batches(sources, labels, max_batch, n_views):
+def src_yuv_frame(fmt, offset: int, h: int, w: int, pitch: int = 0, matrix="JFIF") -> SrcYuv:
+    """The SrcYuv of a frame in one of the common layouts whose first byte will lie at `offset` of the source buffer
+    (qcnn_src_yuv_frame).  fmt: "NV12", "NV21", "I420", "YV12", "I444", "YUY2" or "UYVY"; pitch: bytes between luma rows, 0 =
+    tight; matrix: "JFIF" (full-range BT.601, JPEG), "BT601" or "BT709" (limited range).  Needs no device."""
+    if fmt not in capi.YUV_FORMATS or matrix not in capi.YUV_MATRICES:
+        raise ValueError("src_yuv_frame: format %r / matrix %r; formats %s, matrices %s" % (fmt, matrix, sorted(capi.YUV_FORMATS), sorted(capi.YUV_MATRICES)))
+    out = capi.QcnnSrcYuv()
+    if capi.load().qcnn_src_yuv_frame(capi.YUV_FORMATS[fmt], int(offset), int(h), int(w), int(pitch), capi.YUV_MATRICES[matrix], C.byref(out)):
+        raise QcnnError("src_yuv_frame: a %s frame of %dx%d with pitch %d at offset %d is refused (sides of at least 1, a pitch that holds a "
+                        "row, under 2 GiB)" % (fmt, h, w, pitch, offset))
+    return SrcYuv(*(int(getattr(out, f)) for f in SrcYuv._fields))
+
+
+def pack_yuv_frames(frames, fmt, sizes, matrix="JFIF"):
+    """A list of YCbCr frames (bytes or one-dimensional uint8 arrays, as a decoder wrote them) -> (flat uint8 buffer with the
+    frames back to back, untouched, [SrcYuv]): what the _yuv calls read once the buffer is on the device.  fmt and matrix as
+    src_yuv_frame takes them; sizes: (h, w) or (h, w, pitch) per frame.  Needs no device."""
+    frames = [np.ascontiguousarray(f, np.uint8).tobytes() if isinstance(f, np.ndarray) else bytes(f) for f in frames]
+    sizes = list(sizes)
+    if not frames or len(sizes) != len(frames):
+        raise ValueError("pack_yuv_frames: %d frames, %d sizes" % (len(frames), len(sizes)))
+    descs, off = [], 0
+    for k, (f, size) in enumerate(zip(frames, sizes)):
+        try:
+            d = src_yuv_frame(fmt, off, *size, matrix=matrix) if len(size) == 2 else src_yuv_frame(fmt, off, size[0], size[1], size[2], matrix)
+        except QcnnError as e:
+            raise QcnnError("frame %d: %s" % (k, e)) from None
+        last = max(d.y_offset + (d.h - 1) * d.y_row_stride + (d.w - 1) * d.y_pix_stride,
+                   max(d.cb_offset, d.cr_offset) + ((d.h - 1) >> d.sub_y) * d.c_row_stride + ((d.w - 1) >> d.sub_x) * d.c_pix_stride)
+        if last >= off + len(f):
+            raise QcnnError("frame %d: %d bytes hold no %s frame of %dx%d (its last sample is byte %d)" % (k, len(f), fmt, d.h, d.w, last - off))
+        descs.append(d)
+        off += len(f)
+    return np.frombuffer(bytearray(b"".join(frames)), np.uint8), descs      # a bytearray: the array is writable, as torch wants it
+
+
+def split_batches(sources, labels, max_batch, n_views, yuv=None):
     """Cut a list of per-image sources and their labels into the batches forward_u8_host_batches streams: every batch holds at
     most max_batch // n_views images (n * n_views <= max_batch), the order is kept, the last batch may be ragged.  sources:
     BMP files' contents (bytes: packed by pack_bmp_files and read in place) or uint8 arrays [C][h][w] (pack_sources +
-    src_planar), one kind per call; labels: one class per image, or None.  Returns [(flat, descs, labels_b)], labels_b a
+    src_planar), one kind per call — or, with yuv = (fmt, sizes, matrix), YCbCr frames as pack_yuv_frames takes them; labels: one class per image, or None.  Returns [(flat, descs, labels_b)], labels_b a
     uint16 array or None.  Pure Python: needs no device and pins nothing."""
     srcs = list(sources)
     if not srcs:
@@ -701,6 +801,13 @@ def split_batches(sources, labels, max_batch, n_views):
         if lab.shape != (len(srcs),) or lab.dtype.kind not in "iu" or (lab.size and (lab.min() < 0 or lab.max() > 0xFFFF)):
             raise ValueError("split_batches: labels are one class in [0, 65535] per image")
         lab = lab.astype(np.uint16)
+    if yuv is not None:
+        fmt, sizes, matrix = yuv
+        sizes = list(sizes)
+        if len(sizes) != len(srcs):
+            raise ValueError("split_batches: %d sizes for %d frames" % (len(sizes), len(srcs)))
+        return [pack_yuv_frames(srcs[a:a + per], fmt, sizes[a:a + per], matrix) + (lab[a:a + per].copy() if lab is not None else None,)
+                for a in range(0, len(srcs), per)]
     files = [isinstance(s, (bytes, bytearray, memoryview)) for s in srcs]
     if any(files) and not all(files):
         raise ValueError("split_batches: sources are BMP files' contents or uint8 arrays [C][h][w], not both")
