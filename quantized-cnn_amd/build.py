@@ -45,7 +45,8 @@ def _run(cmd, **kw):
 def build_hip(force: bool = False, extra_flags=()) -> str:
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "qcnn_kernels.h"), os.path.join(CSRC, "qcnn_dev.h"), os.path.join(CSRC, "qcnn_sym8_gather.h"), os.path.join(CSRC, "qcnn_planner.h"), os.path.join(CSRC, "qcnn_src_layout.h"), os.path.join(CSRC, "qcnn_src_yuv.h"), os.path.join(CSRC, "qcnn_pack.h"), os.path.join(ROOT, "include", "qcnn_hip.h")]
+    # every header of csrc/ and the public one: a header nobody listed cannot leave stale objects behind
+    deps = srcs + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "qcnn_hip.h")]
     if force or _newer(HIP_SO, deps):
         objs = []
         for s in srcs:
