@@ -43,6 +43,8 @@
  *   qcnn_calib_gram             (no counterpart: the reference ships finished parameters) second moments of a layer's
  *   / qcnn_quantize_layer_ec    input windows — the windows CalcFeatMap_ConvAprx walks, src/CaffeEva.cc:787-827 — and the
  *                               error-corrected quantisation of Wu et al., CVPR'16, sections 3.2 - 3.3, on them
+ *   qcnn_calib_begin / _arm     (no counterpart) the same second moments accumulated on the device behind every forward, from
+ *   / _read / _end              the layers' input maps where they lie: calibration sets of thousands of images
  *   qcnn_run_layer              CaffeEva::CalcFeatMap on one layer         src/CaffeEva.cc:625-670
  *   qcnn_get_layer_output       featMapLst[l] read-back (parity dumps)     include/CaffeEva.h:109
  *   qcnn_get_layer_ms           swIndvLayerLst / DispElpsTime              src/CaffeEva.cc:297-326
@@ -59,7 +61,7 @@
 extern "C" {
 #endif
 
-#define QCNN_ABI_VERSION 5   /* qcnn_calib_gram / qcnn_quantize_layer_ec are additive: the version stays 5.  5 (round 6): QCNN_OPT_HALF8 (half-panel eight-wave workgroups), qcnn_model_arena_checksum / qcnn_group_arena_checksum,
+#define QCNN_ABI_VERSION 5   /* qcnn_calib_gram / qcnn_quantize_layer_ec / qcnn_calib_begin .. _end are additive: the version stays 5.  5 (round 6): QCNN_OPT_HALF8 (half-panel eight-wave workgroups), qcnn_model_arena_checksum / qcnn_group_arena_checksum,
                               * qcnn_model_mark_loaded drops the lazily built fp16 program tables.  4 (round 5): QCNN_OPT_LUT_MODE 2 = fp16 table storage, 3 = fp16 tables + fp16 sums (the bf16-pair builder
                               * of version 3 is gone); qcnn_set_option rejects out-of-range values of QCNN_OPT_SYM / _SLIDE / _SYM8;
                               * qcnn_model_set_layer_shape accepts up to 256 code words per sub-space; qcnn_group_forward */
@@ -259,6 +261,37 @@ int qcnn_calib_gram(QcnnCtx* ctx, int H, int W, int Cin_total, int grp, int kh, 
 int qcnn_quantize_layer_ec(QcnnCtx* ctx, int Ct, int Cin, int grp, int kh, int kw, int M, int K, int Cs, const float* weights_host,
                            const double* gram_host, const float* ctrd_init_host, const uint8_t* asmt_init_host, int sweeps,
                            double ridge, float* ctrd_out_host, uint8_t* asmt_out_host, double* obj_trace, int* changed_trace);
+/* Resident calibration: qcnn_calib_gram's sums, accumulated on the device behind every forward of a committed model (dense or
+ * quantised), read from each listed layer's INPUT map where the forward left it (image-minor panels [E][128]; kernel
+ * k_ec_gram_panel).  Same conventions (patch index, zeros for out-of-map taps, Ho / Wo) and the same precision contract: fp32
+ * over runs of at most 256 patch rows, fp64 across runs, every entry within gamma_260 * sum |s_p s_q| of its exact value however
+ * many batches are added; no float atomics, symmetric to the bit, the same bits for the same sequence of batches.  The first FC
+ * layer's columns are in the reference's NCHW flatten order d = (c*H + h)*W + w, a later FC layer's are its map's elements.
+ *
+ * qcnn_calib_begin: one zeroed fp64 matrix [grp][P][P] per listed conv / FC layer on the context's device, and arms.  Refused,
+ * with nothing allocated: before commit, a layer that is neither conv nor FC, a layer listed twice, P > 46340, a calibration
+ * already open.  (The input map of a conv / FC layer always exists as a panel map — fused ReLUs alias the rectified map, a fused
+ * LRN + pool pair drops only the map between the two — with one exception, next paragraph.)
+ * LAYER 0 ROUTE: if layer 0 is listed, its input must exist as fm[0] panels while armed.  The float entry points that would
+ * feed a first conv layer straight from the NCHW buffer (QCNN_OPT_KEEP_ALL = 0, the in-place first-layer kernels) take the packed
+ * route for that time: qk_pack_nchw + the panel kernels, whose results differ from the in-place kernels' in the last bits.  The
+ * 8-bit entry points pack anyway.  This is the only way an armed calibration changes a forward's outputs.
+ * While armed, every batch that passes the layer loop — any qcnn_forward* entry point, single call or *_host_batches, any
+ * QCNN_OPT_STREAMS, batches of one to three images included, every chunk of a chunked host batch once — enqueues one launch per
+ * listed layer for its live images (lanes of a ragged panel beyond the batch contribute exactly nothing), on the context's
+ * stream behind the join of the sub-batch streams and in front of whatever could overwrite the maps.
+ * SPLIT RULE: the rows of a launch are cut in units of one (panel, output pixel) = 128 patch rows.  With T upper-triangle tile
+ * pairs (64 x 64) x groups, a launch of `panels` panels runs min(max(1, 2048 / T), 128 MiB / matrix bytes, ceil(units / 2),
+ * 65535) splits of whole two-unit runs (at least 1): a function of the shape and the panel count alone.  Several splits write
+ * fp64 slabs that are added to the matrix in ascending order; one split adds its tiles to the matrix directly.
+ * qcnn_calib_arm(0 / 1): unarmed, nothing is launched and nothing changes.  qcnn_calib_read: blocking; the matrix of a listed
+ * layer (gram_host [grp][P][P], may be NULL) and the patch rows added so far (rows, may be NULL); any number of times, resets
+ * nothing.  qcnn_calib_end frees the matrices; qcnn_model_begin and qcnn_ctx_destroy end an open calibration implicitly.  Without
+ * qcnn_calib_begin no code path differs. */
+int qcnn_calib_begin(QcnnCtx* ctx, const int* layers, int n_layers);
+int qcnn_calib_arm(QcnnCtx* ctx, int on);
+int qcnn_calib_read(QcnnCtx* ctx, int layer, double* gram_host, long long* rows);
+int qcnn_calib_end(QcnnCtx* ctx);
 /* Size of the packed parameter arena (biases, permuted codebooks, permuted assignments). */
 int qcnn_model_arena_bytes(QcnnCtx* ctx, size_t* bytes);
 /* Plan buffers for up to max_batch images.  dev_arena: caller-owned device memory of

@@ -171,6 +171,10 @@ def load():
     lib.qcnn_model_arena_checksum.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     lib.qcnn_quantize_layer.argtypes = [vp, i, i, i, i, i, i, i, f32p, f32p, i, f32p, u8p, C.POINTER(C.c_double), C.POINTER(i)]
     lib.qcnn_calib_gram.argtypes = [vp, i, i, i, i, i, i, i, i, f32p, i, vp, i]
+    lib.qcnn_calib_begin.argtypes = [vp, C.POINTER(i), i]
+    lib.qcnn_calib_arm.argtypes = [vp, i]
+    lib.qcnn_calib_read.argtypes = [vp, i, vp, C.POINTER(C.c_longlong)]
+    lib.qcnn_calib_end.argtypes = [vp]
     lib.qcnn_quantize_layer_ec.argtypes = [vp, i, i, i, i, i, i, i, i, f32p, vp, f32p, u8p, i, C.c_double, f32p, u8p, C.POINTER(C.c_double),
                                            C.POINTER(i)]
     lib.qcnn_plan_conv_query.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(C.c_double), C.POINTER(i)]

@@ -6,6 +6,8 @@
 // G_g = sum over calibration patches of s s^T; Hm = E G.  Kernels (stable names for rocprofv3 --kernel-trace --stats):
 //   k_ec_gram         G_g as a symmetric rank-update, im2col implicit in the loads, v_mfma_f32_16x16x4_f32; fp32 over runs of
 //                     kGramRun patches, fp64 across runs; upper-triangle tiles only, one fp64 slab per row split
+//   k_ec_gram_panel   the same sums from a layer's input where a forward left it, panels [E][128] (qcnn_calib_begin): a column is
+//                     fetched as its 512-byte panel row, 16 bytes a lane, dead lanes zeroed; fp32 over two (panel, pixel) units
 //   k_ec_gram_reduce  slabs added in ascending split order (+ the caller's matrix when accumulating), mirrored
 //   k_ec_identity     G = I when the caller gives no matrix
 //   k_ec_residual     E from the fp32 weights, book and assignments           k_ec_eg         Hm = E G (fp64, LDS tiles)
@@ -151,6 +153,157 @@ __global__ __launch_bounds__(256) void k_ec_gram_reduce(const double* __restrict
     for (int z = 0; z < splits; ++z) sum += slab[(size_t)z * total + src];
     G[i] = sum;
   }
+}
+
+// ---- the same sums from a layer's input where a forward left it: image-minor panels [E][128] (resident calibration) ----
+// The summed axis is (image, output pixel) and the 128 images of one element are 512 contiguous bytes, so the k axis of the MFMA
+// is the contiguous one.  One UNIT = the 128 patch rows of one (panel, output pixel); a column of a unit is one panel row (an
+// element of the map, or zeros for an out-of-map tap).  Two units = one fp32 run of kGramRun rows.
+constexpr int kPanelCols = 8;                    // columns a thread fetches per operand and unit: 256 threads x 16 bytes = 8 rows a pass
+static_assert(kGramRun == 2 * QCNN_PANEL, "an fp32 run is two (panel, output pixel) units");
+static_assert(kGramTile * QCNN_PANEL * sizeof(float) * 2 == 65536, "both operands of a unit fill the static LDS limit exactly");
+
+// Column of tile row `col` in LDS: 128 floats, image k at k ^ swz(col).  A row is 512 bytes = every bank once, so the MFMA
+// operand read (16 columns x 4 consecutive k per instruction) would hit four banks sixteen times over; the XOR moves column
+// col's group of four k to bank group (k / 4) ^ (col % 16): sixteen columns x four k on 64 distinct banks, and a thread's four
+// consecutive images stay one aligned 16-byte store.
+__device__ inline int panel_swz(int col) { return (col & 15) << 2; }
+
+struct PanelCols {                               // per thread: its kPanelCols columns of one operand
+  int yx[kPanelCols];                            // tap row << 16 | tap column
+  int off[kPanelCols];                           // channel offset g * Cg + c (FC: the element itself); -1: past P
+};
+
+__device__ inline void panel_cols(PanelCols& pc, int tile, int g, const QkGramGeom& s, const int* __restrict__ dmap, int cs) {
+#pragma unroll
+  for (int i = 0; i < kPanelCols; ++i) {
+    const GramCol c = gram_col(tile * kGramTile + i * 8 + cs, g, s);
+    pc.yx[i] = (c.y << 16) | c.x;
+    pc.off[i] = !c.ok ? -1 : dmap ? dmap[c.off] : c.off;         // dmap: only with a 1 x 1 window on a map taken as 1 x 1 x D
+  }
+}
+
+// the thread's 16 bytes (images 4 * seg ..) of its columns of unit (panel, oy, ox); lanes of images >= live are zeroed HERE:
+// maps behind the first layer hold bias-derived values in a ragged panel's dead lanes
+__device__ inline void panel_fetch(f32x4 (&v)[kPanelCols], const PanelCols& pc, const float* __restrict__ fm, const QkGramGeom& s,
+                                   size_t panelBase, int oy, int ox, int seg, int live) {
+  const int y0 = oy * s.stride - s.pad, x0 = ox * s.stride - s.pad;
+#pragma unroll
+  for (int i = 0; i < kPanelCols; ++i) {
+    const int iy = y0 + (pc.yx[i] >> 16), ix = x0 + (pc.yx[i] & 0xffff);
+    f32x4 t = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (pc.off[i] >= 0 && iy >= 0 && iy < s.H && ix >= 0 && ix < s.W && 4 * seg < live)
+      t = *reinterpret_cast<const f32x4*>(fm + (panelBase + ((size_t)iy * s.W + ix) * s.C + pc.off[i]) * QCNN_PANEL + 4 * seg);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * seg + j >= live) t[j] = 0.0f;
+    v[i] = t;
+  }
+}
+
+__device__ inline void panel_stage(float* __restrict__ S, const f32x4 (&v)[kPanelCols], int cs, int seg) {
+#pragma unroll
+  for (int i = 0; i < kPanelCols; ++i) {
+    const int col = i * 8 + cs;
+    *reinterpret_cast<f32x4*>(S + col * QCNN_PANEL + ((4 * seg) ^ panel_swz(col))) = v[i];
+  }
+}
+
+// blockIdx.x = upper-triangle tile pair, .y = group, .z = row split (unitsPerSplit units each).  fm: the first of `panels`
+// panels [E][128] that hold nLive images; dmap: the first FC layer's flatten map (column d is element dmap[d]) or nullptr.
+// direct != 0 (one split): out = the resident matrix [grp][P][P], the tile is added to its upper entries and mirrored;
+// otherwise out = slab [split][grp][P][P] as k_ec_gram writes it (k_ec_gram_reduce adds the slabs in ascending order).
+__global__ __launch_bounds__(256) void k_ec_gram_panel(const float* __restrict__ fm, const int* __restrict__ dmap, QkGramGeom s, int nt,
+                                                       int panels, int nLive, int unitsPerSplit, double* __restrict__ out, int direct) {
+  __shared__ __attribute__((aligned(16))) float As[kGramTile * QCNN_PANEL];
+  __shared__ __attribute__((aligned(16))) float Bs[kGramTile * QCNN_PANEL];
+  int ti = 0, rem = blockIdx.x;
+  while (rem >= nt - ti) { rem -= nt - ti; ++ti; }
+  const int tj = ti + rem;
+  const bool diag = ti == tj;
+  const int g = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int seg = tid & 31, cs = tid >> 5;                 // 32 threads x 16 bytes = one 512-byte row; eight rows a pass
+  const int li = lane & 15, lk = lane >> 4;
+  const int hw = s.Ho * s.Wo;
+  const size_t E = (size_t)s.H * s.W * s.C;
+  const long long units = (long long)panels * hw;
+  const long long uBeg = (long long)blockIdx.z * unitsPerSplit;
+  const long long uEnd = uBeg + unitsPerSplit < units ? uBeg + unitsPerSplit : units;
+  const float* __restrict__ Bp = diag ? As : Bs;
+  PanelCols pa, pb;
+  panel_cols(pa, ti, g, s, dmap, cs);
+  if (!diag) panel_cols(pb, tj, g, s, dmap, cs);
+  f32x4 acc[2][2];
+  double dacc[2][2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      acc[a][b] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dacc[a][b][r] = 0.0;
+    }
+  f32x4 va[kPanelCols], vb[kPanelCols];
+  auto fetch = [&](long long u) {
+    const int panel = (int)(u / hw), pix = (int)(u - (long long)panel * hw);
+    const int oy = pix / s.Wo, ox = pix - oy * s.Wo;
+    const int live = min(nLive - panel * QCNN_PANEL, QCNN_PANEL);
+    panel_fetch(va, pa, fm, s, (size_t)panel * E, oy, ox, seg, live);
+    if (!diag) panel_fetch(vb, pb, fm, s, (size_t)panel * E, oy, ox, seg, live);
+  };
+  if (uBeg < uEnd) fetch(uBeg);
+  int inRun = 0;
+  for (long long u = uBeg; u < uEnd; ++u) {
+    __syncthreads();                                       // the previous unit's operand reads have passed
+    panel_stage(As, va, cs, seg);
+    if (!diag) panel_stage(Bs, vb, cs, seg);
+    __syncthreads();
+    if (u + 1 < uEnd) fetch(u + 1);                        // the next unit's rows fly under this unit's MFMAs
+    const int sw = li << 2;
+#pragma unroll 8
+    for (int k0 = 0; k0 < QCNN_PANEL; k0 += 4) {
+      float a[2], b[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        a[h] = As[(wr * 32 + h * 16 + li) * QCNN_PANEL + ((k0 + lk) ^ sw)];
+        b[h] = Bp[(wc * 32 + h * 16 + li) * QCNN_PANEL + ((k0 + lk) ^ sw)];
+      }
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[x], b[y], acc[x][y], 0, 0, 0);
+    }
+    if (++inRun == kGramRun / QCNN_PANEL || u + 1 == uEnd) {
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dacc[x][y][r] += (double)acc[x][y][r];
+          acc[x][y] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+      inRun = 0;
+    }
+  }
+  // D[(lane >> 4) * 4 + r][lane & 15]
+  const size_t pp = (size_t)s.P * s.P;
+  double* __restrict__ dst = out + (direct ? (size_t)g : (size_t)blockIdx.z * gridDim.y + g) * pp;
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int p = ti * kGramTile + wr * 32 + x * 16 + lk * 4 + r, q = tj * kGramTile + wc * 32 + y * 16 + li;
+        if (p >= s.P || q >= s.P) continue;
+        if (!direct) { dst[(size_t)p * s.P + q] = dacc[x][y][r]; continue; }
+        if (p > q) continue;                               // a diagonal tile's lower half: its mirror image writes it
+        const double sum = dst[(size_t)p * s.P + q] + dacc[x][y][r];
+        dst[(size_t)p * s.P + q] = sum;
+        if (p != q) dst[(size_t)q * s.P + p] = sum;
+      }
 }
 
 __global__ __launch_bounds__(256) void k_ec_identity(double* __restrict__ G, int P, int grp) {
@@ -462,6 +615,36 @@ hipError_t qk_ec_gram(const float* in, const QkGramGeom& s, long long rowsPerSpl
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_ec_gram_reduce, dim3(grid_for((size_t)s.grp * s.P * s.P, 16384)), dim3(256), 0, st, slab, G, s.P, s.grp, splits,
                      accumulate);
+  return hipGetLastError();
+}
+
+// k_ec_gram_panel's rows are cut in units of one (panel, output pixel) = 128 patch rows; a split is whole fp32 runs of two
+// units.  As many splits as fill the chip (2048 workgroups) with the shape's tile pairs, at most one per run, slabs of at most
+// maxSlabBytes in all: a function of the shape and the panel count alone.  *splits == 1: no slab, the tiles go straight into
+// the resident matrix.
+long long qk_ec_gram_panel_units_per_split(const QkGramGeom& s, int panels, size_t maxSlabBytes, int* splits) {
+  const long long nt = qk_ec_gram_tiles(s.P), wgs = nt * (nt + 1) / 2 * s.grp;
+  const long long units = (long long)panels * s.Ho * s.Wo;
+  const long long runs = (units + 1) / 2;
+  const size_t one = (size_t)s.grp * s.P * s.P * sizeof(double);
+  long long want = std::max<long long>(1, 2048 / wgs);
+  want = std::min<long long>(want, std::max<long long>(1, (long long)(maxSlabBytes / one)));
+  want = std::max<long long>(1, std::min<long long>(std::min<long long>(want, runs), 65535));
+  const long long per = (runs + want - 1) / want * 2;
+  *splits = (int)std::max<long long>(1, (units + per - 1) / per);
+  return per;
+}
+
+// G += the sums over the nLive images of `panels` panels at fm.  splits > 1: through slab (splits * grp * P * P doubles)
+hipError_t qk_ec_gram_panel(const float* fm, const int* dmap, const QkGramGeom& s, int panels, int nLive, long long unitsPerSplit,
+                            int splits, double* slab, double* G, hipStream_t st) {
+  const int nt = qk_ec_gram_tiles(s.P);
+  const int direct = splits == 1;
+  hipLaunchKernelGGL(k_ec_gram_panel, dim3(nt * (nt + 1) / 2, s.grp, splits), dim3(256), 0, st, fm, dmap, s, nt, panels, nLive,
+                     (int)unitsPerSplit, direct ? G : slab, direct);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || direct) return e;
+  hipLaunchKernelGGL(k_ec_gram_reduce, dim3(grid_for((size_t)s.grp * s.P * s.P, 16384)), dim3(256), 0, st, slab, G, s.P, s.grp, splits, 1);
   return hipGetLastError();
 }
 

@@ -153,6 +153,15 @@ struct QcnnCtx {
     unsigned long long* hits = nullptr;               // [5] on the device, zeroed at every call's entry
     unsigned long long* pinHits = nullptr;
   } u8s;
+  // qcnn_calib_begin .. qcnn_calib_end: one resident fp64 matrix [grp][P][P] per listed layer; while armed, run_layers adds the
+  // second moments of every batch's input maps to them (k_ec_gram_panel) behind the layers, on the context's stream
+  struct Calib {
+    struct Layer { int layer = 0; QkGramGeom g = {}; double* G = nullptr; long long rows = 0; };
+    bool active = false, armed = false;
+    bool wantsInput = false;         // layer 0 is listed: fm[0] must exist as panels, float entry points take the packed route
+    std::vector<Layer> layers;
+    double* slab = nullptr;          // scratch of the split launches, sized for maxPanels at begin
+  } calib;
   int lastN = 0;
   std::vector<float*> lastFm;        // pointer table of the last forward
 
@@ -386,7 +395,18 @@ void drop_f16_programs(LayerShape& s) {
     }
 }
 
+constexpr size_t kCalibSlabBytes = (size_t)128 << 20;   // cap of the resident calibration's split scratch (part of its split rule)
+
+// the resident calibration matrices (hipFree waits for the launches that still write them)
+void calib_free(QcnnCtx* c) {
+  for (QcnnCtx::Calib::Layer& q : c->calib.layers)
+    if (q.G) (void)hipFree(q.G);
+  if (c->calib.slab) (void)hipFree(c->calib.slab);
+  c->calib = QcnnCtx::Calib();
+}
+
 void free_model(QcnnCtx* c) {
+  calib_free(c);                                         // a calibration belongs to the model it was begun on
   for (LayerShape& s : c->shapes) drop_f16_programs(s);
   for (float* p : c->fmBuf) if (p) (void)hipFree(p);
   c->fmBuf.clear();
@@ -851,6 +871,7 @@ int lrn_pool_min_blocks() {
 // sub-space of <= 4 dims: exactly what the operand loads of one stage touch) and K = 128 or the exact builder.
 bool direct_input(const QcnnCtx* c, int n) {
   if (c->keepAll || c->L == 0 || c->layers[0].type != QCNN_CONV) return false;
+  if (c->calib.armed && c->calib.wantsInput) return false;     // an armed calibration of layer 0 reads fm[0] as panels
   // the images of THIS forward inside 4 GiB: the in-place kernels keep image offsets in 32 bits
   if ((unsigned long long)n * c->inC * c->inH * c->inW * sizeof(float) >= (1ull << 32)) return false;
   // a first layer that runs through its decoded code words reads packed panels — unless its kernel has the NCHW form
@@ -861,6 +882,25 @@ bool direct_input(const QcnnCtx* c, int n) {
   // image past the caller's buffer)
   if (c->shapes[0].dense || c->shapes[0].M != 1) return false;
   return c->inC / d.grpCnt <= 4 && (c->lutMode == 0 || c->shapes[0].K == 128);
+}
+
+// Armed calibration: the second moments of the panels [pa, pb) of a batch of n images, added to the resident matrices on the
+// context's stream — behind the join of the sub-batch streams, in front of whatever the caller enqueues next (the next batch's
+// pack kernel, the event that hands a source buffer back).  fm: the pointer table of this call.
+int calib_enqueue(QcnnCtx* c, const std::vector<float*>& fm, int n, int pa, int pb) {
+  const int nLive = std::min(n, pb * QCNN_PANEL) - pa * QCNN_PANEL;
+  for (QcnnCtx::Calib::Layer& q : c->calib.layers) {
+    const int l = q.layer;
+    if (!fm[l]) return fail(c, "calibration: the input map of layer %d does not exist as panels in this forward", l);
+    int splits = 1;
+    const long long per = qk_ec_gram_panel_units_per_split(q.g, pb - pa, kCalibSlabBytes, &splits);
+    const int* dmap = c->shapes[l].hasDmap ? arena_at<const int>(c, c->shapes[l].offDmap) : nullptr;
+    const hipError_t e = qk_ec_gram_panel(fm[l] + (size_t)pa * fm_elems(c, l) * QCNN_PANEL, dmap, q.g, pb - pa, nLive, per, splits,
+                                          c->calib.slab, q.G, c->stream);
+    if (e != hipSuccess) return fail(c, "calibration of layer %d: launch failed: %s", l, hipGetErrorString(e));
+    q.rows += (long long)nLive * q.g.Ho * q.g.Wo;
+  }
+  return 0;
 }
 
 // The layers of one forward.  The batch is cut into up to nStreams sub-batches of whole panels; sub-batch 0
@@ -953,6 +993,7 @@ int run_layers(QcnnCtx* c, int n, const float* inNchw = nullptr, int pa = 0, int
     HIP_TRY(c, hipEventRecord(c->evJoin[k - 1], c->aux[k - 1]));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evJoin[k - 1], 0));
   }
+  if (c->calib.armed && calib_enqueue(c, fm, n, pa, pb)) return 1;
   if (prof) c->profCount++;
   // what can be read back afterwards: a map exists only if every chunk of the batch materialised it
   if (pa == 0 || (int)c->lastFm.size() != c->L + 1) {
@@ -1435,6 +1476,107 @@ int qcnn_quantize_layer_ec(QcnnCtx* c, int Ct, int Cin, int grp, int kh, int kw,
   HIP_TRY(c, hipStreamSynchronize(st));
   for (int m = 0; m < M; ++m)
     for (int n = 0; n < s.N; ++n) asmt_out[(size_t)n * M + m] = a[(size_t)m * s.N + n];
+  return 0;
+}
+
+int qcnn_calib_begin(QcnnCtx* c, const int* layers, int n_layers) {
+  if (!c) return fail(nullptr, "qcnn_calib_begin: ctx == NULL");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->committed) return fail(c, "qcnn_calib_begin: model not committed");
+  if (c->calib.active) return fail(c, "qcnn_calib_begin: a calibration is already open (qcnn_calib_end closes it)");
+  if (!layers || n_layers <= 0) return fail(c, "qcnn_calib_begin: no layers");
+  // every layer is checked before anything is allocated
+  std::vector<QcnnCtx::Calib::Layer> list;
+  size_t slabBytes = 0;
+  for (int i = 0; i < n_layers; ++i) {
+    const int l = layers[i];
+    if (l < 0 || l >= c->L) return fail(c, "qcnn_calib_begin: layer %d out of range", l);
+    const QcnnLayerDesc& d = c->layers[l];
+    if (d.type != QCNN_CONV && d.type != QCNN_FCNT) return fail(c, "qcnn_calib_begin: layer %d is neither conv nor FC", l);
+    for (const QcnnCtx::Calib::Layer& q : list)
+      if (q.layer == l) return fail(c, "qcnn_calib_begin: layer %d is listed twice", l);
+    // the input map of a conv / FC layer is never fused away: an LRN + pool pair drops the map BETWEEN the two, a fused ReLU
+    // aliases a map that holds the rectified values, dropout is a copy.  Only fm[0] can be missing (the NCHW input read in
+    // place), and that route is switched off while layer 0 is armed; a map without a buffer would be a planning error
+    if (l > 0 && !c->fmBuf[l] && c->layers[l - 1].type != QCNN_DRPT)
+      return fail(c, "qcnn_calib_begin: the input map of layer %d never exists as a panel map", l);
+    QcnnCtx::Calib::Layer q;
+    q.layer = l;
+    QkGramGeom& s = q.g;
+    const bool conv = d.type == QCNN_CONV;
+    const FmDims& a = c->dims[l];
+    s.H = conv ? a.h : 1; s.W = conv ? a.w : 1; s.C = conv ? a.c : (int)fm_elems(c, l);
+    s.grp = conv ? d.grpCnt : 1; s.Cg = s.C / s.grp;
+    s.kh = s.kw = conv ? d.knlSiz : 1; s.stride = conv ? d.stride : 1; s.pad = conv ? d.padSiz : 0;
+    s.Ho = conv_out(s.H, s.kh, s.stride, s.pad);
+    s.Wo = conv_out(s.W, s.kw, s.stride, s.pad);
+    const long long Pll = (long long)s.kh * s.kw * s.Cg;
+    if (Pll > 46340) return fail(c, "qcnn_calib_begin: layer %d: patch length %lld is too large", l, Pll);    // P * P stays below 2^31
+    s.P = (int)Pll;
+    s.rows = 0;
+    if ((long long)c->maxPanels * s.Ho * s.Wo > INT_MAX) return fail(c, "qcnn_calib_begin: layer %d: too many output pixels per batch", l);
+    int splits = 1;                                      // the most any panel count asks for (rounding: not monotonic)
+    for (int p = 1; p <= c->maxPanels; ++p) {
+      int z = 1;
+      (void)qk_ec_gram_panel_units_per_split(s, p, kCalibSlabBytes, &z);
+      splits = std::max(splits, z);
+    }
+    if (splits > 1) slabBytes = std::max(slabBytes, (size_t)splits * s.grp * s.P * s.P * sizeof(double));
+    list.push_back(q);
+  }
+  for (QcnnCtx::Calib::Layer& q : list) {
+    const size_t bytes = (size_t)q.g.grp * q.g.P * q.g.P * sizeof(double);
+    hipError_t e = hipMalloc(&q.G, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(q.G, 0, bytes, c->stream);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      for (QcnnCtx::Calib::Layer& r : list) if (r.G) (void)hipFree(r.G);
+      return fail(c, "qcnn_calib_begin: layer %d: %zu bytes for its matrix: %s", q.layer, bytes, hipGetErrorString(e));
+    }
+  }
+  double* slab = nullptr;
+  if (slabBytes && hipMalloc(&slab, slabBytes) != hipSuccess) {
+    (void)hipGetLastError();
+    for (QcnnCtx::Calib::Layer& r : list) (void)hipFree(r.G);
+    return fail(c, "qcnn_calib_begin: %zu bytes of split scratch do not fit the device", slabBytes);
+  }
+  c->calib.layers = list;
+  c->calib.slab = slab;
+  c->calib.wantsInput = false;
+  for (const QcnnCtx::Calib::Layer& q : list) c->calib.wantsInput = c->calib.wantsInput || q.layer == 0;
+  c->calib.active = c->calib.armed = true;
+  return 0;
+}
+
+int qcnn_calib_arm(QcnnCtx* c, int on) {
+  if (!c) return fail(nullptr, "qcnn_calib_arm: ctx == NULL");
+  if (!c->calib.active) return fail(c, "qcnn_calib_arm: no calibration is open (qcnn_calib_begin)");
+  c->calib.armed = on != 0;
+  return 0;
+}
+
+int qcnn_calib_read(QcnnCtx* c, int layer, double* gram_host, long long* rows) {
+  if (!c) return fail(nullptr, "qcnn_calib_read: ctx == NULL");
+  if (!c->calib.active) return fail(c, "qcnn_calib_read: no calibration is open (qcnn_calib_begin)");
+  for (const QcnnCtx::Calib::Layer& q : c->calib.layers) {
+    if (q.layer != layer) continue;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (gram_host) {
+      HIP_TRY(c, hipMemcpyAsync(gram_host, q.G, (size_t)q.g.grp * q.g.P * q.g.P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (rows) *rows = q.rows;
+    return 0;
+  }
+  return fail(c, "qcnn_calib_read: layer %d is not part of the open calibration", layer);
+}
+
+int qcnn_calib_end(QcnnCtx* c) {
+  if (!c) return fail(nullptr, "qcnn_calib_end: ctx == NULL");
+  if (!c->calib.active) return fail(c, "qcnn_calib_end: no calibration is open (qcnn_calib_begin)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  calib_free(c);
   return 0;
 }
 

@@ -525,6 +525,12 @@ long long qk_ec_gram_rows_per_split(const QkGramGeom& s, size_t maxSlabBytes, in
 // slab: splits * grp * P * P doubles; G = (accumulate ? G : 0) + the slabs in ascending order, mirrored
 hipError_t qk_ec_gram(const float* in, const QkGramGeom& s, long long rowsPerSplit, int splits, double* slab, double* G, int accumulate,
                       hipStream_t st);
+// The same sums from `panels` panels [E][128] at fm that hold nLive images (s.H, s.W, s.C: the map; an FC layer: 1 x 1 x D, dmap =
+// the first FC layer's flatten map or nullptr), ADDED to G.  (panel, output pixel) units per split and the split count: a
+// function of the shape and the panel count alone; splits == 1 needs no slab
+long long qk_ec_gram_panel_units_per_split(const QkGramGeom& s, int panels, size_t maxSlabBytes, int* splits);
+hipError_t qk_ec_gram_panel(const float* fm, const int* dmap, const QkGramGeom& s, int panels, int nLive, long long unitsPerSplit,
+                            int splits, double* slab, double* G, hipStream_t st);
 hipError_t qk_ec_identity(double* G, int P, int grp, hipStream_t st);
 int qk_ec_objective_blocks(const QkEcShape& s);
 hipError_t qk_ec_evaluate(const float* w, const float* ctrd, const uint8_t* asmt, const double* G, double* E, double* Hm, double* partial,

@@ -259,6 +259,37 @@ class QcnnEngine:
                                            gram.ctypes.data, 1 if acc else 0))
         return gram
 
+    def calib_begin(self, layers):
+        """Open a resident calibration on the loaded model (qcnn_calib_begin): one zeroed float64 matrix [grp][P][P] per listed
+        conv / FC layer on the device, armed.  While armed, every batch of every forward call adds the second moments of those
+        layers' input maps, where they lie.  With layer 0 listed, float forwards take the packed input route (qcnn_hip.h)."""
+        ls = [int(l) for l in layers]
+        arr = (C.c_int * max(len(ls), 1))(*ls)
+        self._chk(self.lib.qcnn_calib_begin(self.h, arr, len(ls)))
+        self._calib_shapes = {}
+        for l in ls:
+            ly = self.layers[l]
+            h, w, ch = self.fm_dims(l)
+            grp, taps, cin = (int(ly["grp"]), int(ly["knl"]) ** 2, ch) if ly["type"] == CONV else (1, 1, h * w * ch)
+            self._calib_shapes[l] = (grp, taps * cin // grp, taps * cin // grp)
+
+    def calib_arm(self, on):
+        """Arm (True) or disarm (False) the open calibration (qcnn_calib_arm): unarmed forwards add nothing."""
+        self._chk(self.lib.qcnn_calib_arm(self.h, 1 if on else 0))
+
+    def calib_read(self, layer):
+        """(gram float64 [grp][P][P], patch rows added so far) of a listed layer (qcnn_calib_read); blocking, resets nothing."""
+        shape = getattr(self, "_calib_shapes", {}).get(int(layer))
+        gram = np.empty(shape, np.float64) if shape else None
+        rows = C.c_longlong(0)
+        self._chk(self.lib.qcnn_calib_read(self.h, int(layer), gram.ctypes.data if shape else None, C.byref(rows)))
+        return gram, int(rows.value)
+
+    def calib_end(self):
+        """Free the calibration's matrices (qcnn_calib_end); loading another model does the same."""
+        self._calib_shapes = {}
+        self._chk(self.lib.qcnn_calib_end(self.h))
+
     def quantize_layer_ec(self, weights, M, K, Cs, gram, ctrd, asmt, grp=1, sweeps=DEFAULT_EC_SWEEPS, ridge=DEFAULT_EC_RIDGE):
         """Error-corrected refinement of a quantisation of one layer (qcnn_quantize_layer_ec): from the book ``ctrd`` [M][K][Cs]
         and assignments ``asmt`` (file order, quantize_layer's output) minimise the response error e^T G e against ``gram``

@@ -7,6 +7,7 @@ MATLAB code that was not released), run on the GPU through ``QcnnEngine.quantize
                         pyoracle.COracle.set_params take, plus per-layer statistics
 ``calibrate``           second moments of every conv / FC layer's input on calibration images (the dense network's own
                         feature maps), for the error-corrected refinement ``quantize_model(..., calib=...)`` runs after k-means
+``calibrate_u8``        the same on 8-bit source images streamed from host memory, accumulated on the device
 ``quantize_param_dir``  reads ``<pfx>.biasVec`` + ``convKnl`` / ``fcntWei`` files, writes ``biasVec`` + ``ctrdLst`` +
                         ``asmtLst.cbn`` (minimum bits, CaffePara::CalcBitCntPerEle) for the reference's LoadLayerPara
 
@@ -70,15 +71,33 @@ def layer_input(layers, i, fm_nhwc):
     return np.ascontiguousarray(x)
 
 
-def calibrate(eng, in_chw, layers, dense, imgs, chunk=32):
+def _read_resident(eng, dense):
+    try:
+        return {i: eng.calib_read(i)[0] for i in sorted(dense)}
+    finally:
+        eng.calib_end()
+
+
+def calibrate(eng, in_chw, layers, dense, imgs, chunk=32, resident=False):
     """{layer: gram [grp][P][P] float64} for every layer of ``dense``: the dense model (load_dense_model, every feature map kept)
     forwards ``imgs`` [n][C][H][W] in chunks, and each conv / FC layer's INPUT map goes to ``eng.calib_gram``, accumulating.
     Every layer sees the dense network's activations, so layers are corrected independently of each other.  Loads a model
-    into ``eng``: whatever it held before is replaced, and QCNN_OPT_KEEP_ALL is left at 1 (the library's default)."""
+    into ``eng``: whatever it held before is replaced, and QCNN_OPT_KEEP_ALL is left at 1 (the library's default).
+    ``resident=True``: the sums are accumulated on the device behind every chunk's forward (eng.calib_begin on every layer of
+    ``dense``) and read once at the end — no map travels to the host and back; same dict, equal within the kernels' bound."""
     imgs = np.ascontiguousarray(imgs, np.float32)
     chunk = max(1, min(int(chunk), len(imgs)))
     eng.set_option(capi.OPT_KEEP_ALL, 1)
     eng.load_dense_model(in_chw, layers, dense, chunk)
+    if resident:
+        eng.calib_begin(sorted(dense))
+        try:
+            for n0 in range(0, len(imgs), chunk):
+                eng.forward_host(imgs[n0:n0 + chunk], want_prob=False, want_top5=False)
+        except BaseException:
+            eng.calib_end()
+            raise
+        return _read_resident(eng, dense)
     grams = {}
     for n0 in range(0, len(imgs), chunk):
         part = imgs[n0:n0 + chunk]
@@ -87,6 +106,25 @@ def calibrate(eng, in_chw, layers, dense, imgs, chunk=32):
             x = layer_input(layers, i, eng.layer_output(i, len(part)))
             grams[i] = eng.calib_gram(x, layer_geom(layers, i), grams.get(i))
     return grams
+
+
+def calibrate_u8(eng, in_chw, layers, dense, batches, full_hw, mean=None, views=None, mode="strict", max_batch=None):
+    """``calibrate(resident=True)`` on 8-bit source images streamed from host memory (eng.forward_u8_host_batches): ``batches``
+    is what engine.split_batches returns ([(flat, descs, labels)], B, G, R or YCbCr descriptors; the labels are not used),
+    ``full_hw`` / ``mean`` / ``views`` / ``mode`` as forward_u8_host_batches takes them.  Every view of every image is one
+    calibration input.  ``max_batch``: batch slots the model is committed for (default: the largest batch x views)."""
+    V = 1 if views is None else len(views)
+    if max_batch is None:
+        max_batch = max(len(b[1]) for b in batches) * V
+    eng.set_option(capi.OPT_KEEP_ALL, 1)
+    eng.load_dense_model(in_chw, layers, dense, int(max_batch))
+    eng.calib_begin(sorted(dense))
+    try:
+        eng.forward_u8_host_batches([(b[0], b[1]) for b in batches], full_hw, mean, views, mode, want=(False, False, False))
+    except BaseException:
+        eng.calib_end()
+        raise
+    return _read_resident(eng, dense)
 
 
 def quantize_model(eng, in_chw, layers, dense, spec=None, max_iter=DEFAULT_MAX_ITER, calib=None, sweeps=DEFAULT_EC_SWEEPS,
@@ -140,10 +178,11 @@ def read_dense_param_dir(dir_path, prefix, layers):
 
 
 def quantize_param_dir(src_dir, src_pfx, dst_dir, dst_pfx, model, eng=None, spec=None, max_iter=DEFAULT_MAX_ITER, calib_images=None,
-                       sweeps=DEFAULT_EC_SWEEPS, ridge=DEFAULT_EC_RIDGE):
+                       sweeps=DEFAULT_EC_SWEEPS, ridge=DEFAULT_EC_RIDGE, calib_sources=None):
     """Quantise a dense parameter directory into a Q-CNN one.  ``model``: a name of topology.MODELS or (in_chw, layers).
     ``eng``: anything with QcnnEngine.quantize_layer's signature (default: a QcnnEngine on device 0).  ``calib_images``
     ([n][C][H][W]): error-corrected on them (calibrate + quantize_model(calib=...)); ``eng`` then loses the model it held.
+    ``calib_sources`` = (batches, full_hw, mean, views, mode) instead: error-corrected on 8-bit sources (calibrate_u8).
     Returns the stats of quantize_model."""
     in_chw, layers = _model_tables(model)
     dense = read_dense_param_dir(src_dir, src_pfx, layers)
@@ -151,7 +190,12 @@ def quantize_param_dir(src_dir, src_pfx, dst_dir, dst_pfx, model, eng=None, spec
     if own:
         eng = QcnnEngine(0)
     try:
+        if calib_images is not None and calib_sources is not None:
+            raise ValueError("quantize_param_dir: calib_images or calib_sources, not both")
         calib = calibrate(eng, in_chw, layers, dense, calib_images) if calib_images is not None else None
+        if calib_sources is not None:
+            batches, full_hw, mean, views, mode = calib_sources
+            calib = calibrate_u8(eng, in_chw, layers, dense, batches, full_hw, mean, views, mode)
         params, stats = quantize_model(eng, in_chw, layers, dense, spec=spec, max_iter=max_iter, calib=calib, sweeps=sweeps, ridge=ridge)
     finally:
         if own:
