@@ -57,6 +57,41 @@ def test_batches_equal_one_forward_per_batch(pinned):
             engine.host_unregister(allimgs)
 
 
+def test_debug_schedule_prints_one_ordered_line_per_batch(tmp_path):
+    """QCNN_DEBUG_PIPELINE=1 (read once per process: a fresh child) through the one batch schedule both streamed paths share:
+    forward_host_batches on batches of 130, 1 and 257 images, then a one-view strict 8-bit stream of three batches.  Each call
+    prints exactly one line per batch with that batch's image count; inside a line an interval does not end before it starts
+    and the layers do not start before the upload has ended (values are printed to 0.01 ms: two roundings, 0.02 ms of slack);
+    the results are bit-equal to the same calls made here without the variable."""
+    import re
+    import subprocess
+    import sys
+    import pipeline_debug_calls as calls
+    want = calls.run_calls()
+    out = str(tmp_path / "debug.npz")
+    env = dict(os.environ, QCNN_DEBUG_PIPELINE="1")
+    r = subprocess.run([sys.executable, calls.__file__, out], capture_output=True, text=True, timeout=300, env=env,
+                       cwd=os.path.dirname(calls.__file__))
+    assert r.returncode == 0, r.stderr[-3000:]
+    err = r.stderr.split(calls.MARK)
+    assert len(err) == 2, r.stderr[-3000:]
+    line = re.compile(r"^\[qcnn pipeline\] batch (\d+) \((\d+) images\): upload (-?\d+\.\d\d) -> (-?\d+\.\d\d) ms, "
+                      r"layers (-?\d+\.\d\d) -> (-?\d+\.\d\d) ms$")
+    for text, sizes in zip(err, (calls.FLOAT_SIZES, calls.U8_COUNTS)):
+        printed = [ln for ln in text.splitlines() if "[qcnn pipeline]" in ln]
+        print("\n".join(printed))
+        found = [line.match(ln) for ln in printed]
+        assert all(found), printed
+        assert [(int(m.group(1)), int(m.group(2))) for m in found] == list(enumerate(sizes)), printed
+        for m in found:
+            up0, up1, ly0, ly1 = (float(m.group(j)) for j in (3, 4, 5, 6))
+            assert up1 >= up0 and ly1 >= ly0 and ly0 >= up1 - 0.02, m.group(0)
+    got = np.load(out)
+    assert sorted(got.files) == sorted(want)
+    for name, w in want.items():
+        assert got[name].dtype == w.dtype and got[name].shape == w.shape and got[name].tobytes() == w.tobytes(), name
+
+
 def test_large_host_batch_is_chunked_without_changing_results():
     """qcnn_forward_host on the fast path cuts >= 4 panels into two-panel chunks (upload under compute); layer-for-
     layer mode runs one launch.  Same bits either way (panel kernels: an image does not depend on its batch)."""
