@@ -161,11 +161,19 @@ enum {
                               per segment); 2 = the tile form whenever eligible, 3 = the sliding form whenever eligible (tests); 0 = never.
                               Same table entries in the same order: bit-identical to the other f32 table kernels.
                               qcnn_get_layer_split reports (-9, 1) / (-10, segments per column) */
-  QCNN_OPT_DEC_BF16SPLIT = 14, /* 1 (default): a first layer read in place (QCNN_OPT_DIRECT_DEC) whose code words fit the LDS as two
-                              bf16 pieces (Cin knl^2 rounded up to 32, times the channels, times 4 bytes <= 158 KB) computes its products
-                              on the bf16 matrix pipe at fp32 accuracy: activations and code words split exactly into three bf16 pieces
-                              each, the six cross terms down to order 2^-16 summed in fp32 (k_conv_dec_nchw_split).  Not bit-identical
-                              to 0 = the f32 matrix instructions (k_conv_dec_nchw); batch-size invariant like it. */
+  QCNN_OPT_DEC_BF16SPLIT = 14, /* A first layer read in place (QCNN_OPT_DIRECT_DEC) whose code words fit the LDS as two 16-bit
+                              pieces (Cin knl^2 rounded up to 32, times the channels, times 4 bytes <= 158 KB) computes its products
+                              on the 16-bit matrix pipe at fp32 accuracy.  1: activations and code words split exactly into three bf16
+                              pieces each, the six cross terms down to order 2^-16 summed in fp32 (k_conv_dec_nchw_split).  2 (default):
+                              two fp16 pieces each, scaled by exact powers of two (activations by 64, code words by a per-layer scale
+                              that puts the largest into [2^13, 2^14]), the three cross terms x2 w1, x1 w2, x1 w1 summed in fp32
+                              (k_conv_dec_nchw_f16: half the matrix instructions; a product is within 3 x 2^-22 of exact).  Input
+                              values outside [-1023, 1023], NaN and Inf included, are detected per work item and image, and those
+                              images' results of the item are recomputed in form 1 by a second launch: they carry form 1's bits, no
+                              other image's result changes.  A layer without such a scale (all code words zero, a largest |code word|
+                              that is not a normal float in [2^-107, 2^20), a bias that is not finite or beyond 2^100 / (64 scale)) runs
+                              form 1.  Neither is bit-identical to 0 = the f32 matrix instructions (k_conv_dec_nchw); all three are
+                              batch-size invariant.  Other values are refused.  qcnn_get_layer_dec_form reports what ran. */
   QCNN_OPT_HOST_CHUNK = 6, /* panels per chunk (default 2) of a qcnn_forward_host batch of at least two chunks: every chunk is
                               uploaded on a copy stream and its layers start when it has arrived, so the upload of chunk
                               k + 1 runs under the layers of chunk k; all chunks fill the same whole-batch feature maps.
@@ -644,6 +652,13 @@ int qcnn_run_layer(QcnnCtx* ctx, int layer, const float* in_host, int n, float* 
  * and FC layers): -11, *slices = 1 — only when they took the launch: a layer whose shape they do not cover (a tap window x K beyond
  * their LDS table, an FC code book whose K is not a multiple of 4) reports the panel kernel that ran instead. */
 int qcnn_get_layer_split(QcnnCtx* ctx, int layer, int* tiles_unsplit, int* slices);
+/* A first conv layer that read the NCHW batch in place (qcnn_get_layer_split reports (-3, 2)): *form = the decoded form its last
+ * launch ran — 0 f32 matrix instructions, 1 three bf16 pieces, 2 two fp16 pieces (QCNN_OPT_DEC_BF16SPLIT) —, -1 for any other
+ * layer or kernel; *fallback_pairs = the (work item, image) pairs whose results the fix-up launch of form 2 recomputed in form 1
+ * because the item's windows held a value outside [-1023, 1023] (NaN and Inf included), summed over the sub-batch launches of the
+ * last forward (of its last chunk, for a chunked host batch); 0 for the other forms.  Either pointer may be NULL.  Blocking:
+ * it waits for the context's streams and reads the guard regions back — for tests and diagnosis. */
+int qcnn_get_layer_dec_form(QcnnCtx* ctx, int layer, int* form, long long* fallback_pairs);
 /* Sliding kernel: the row segments [seg_beg9[i], seg_beg9[i + 1]) every output column of the last launch of `layer` was
  * cut into (*n_seg of them; 0 when the layer ran the tile kernel). */
 int qcnn_get_layer_segments(QcnnCtx* ctx, int layer, int* seg_beg9, int* n_seg);

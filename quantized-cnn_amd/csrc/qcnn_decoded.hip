@@ -326,7 +326,8 @@ hipError_t launch_dec(const DecParams& p, hipStream_t st) {
 #endif
 #ifndef NCHW_VAR
 #define NCHW_VAR 0      // timing experiments (scripts/variants_nchw.sh): 1 no operand loads, 2 no products, 4 no stores,
-#endif                  // 8 no split, 16 no w3 loads (the last two: k_conv_dec_nchw_split)
+#endif                  // 8 no split (both split kernels), 16 no w3 loads (k_conv_dec_nchw_split only), 32 no fix-up launch
+                        // behind k_conv_dec_nchw_f16
 
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
@@ -433,8 +434,9 @@ __device__ __forceinline__ void nchw_bias(const DecParams& p, const NchwItem& w,
 // The image values are the rows of a product (A), the code words its columns (B): lane (li, kq) holds channel li of the tile
 // at position kq >> 1 of the tile's two for the FOUR CONSECUTIVE images 4 (kq & 1) .. + 3 of its eight — one 16-byte store
 // per tile
-template <int CT, int IT>
-__device__ __forceinline__ void nchw_store(const DecParams& p, const NchwItem& w, const f32x4 (&acc)[CT][IT]) {
+// SCALED (k_conv_dec_nchw_f16): the sums are in units of 1 / outScale, an exact power of two
+template <int CT, int IT, bool SCALED = false>
+__device__ __forceinline__ void nchw_store(const DecParams& p, const NchwItem& w, const f32x4 (&acc)[CT][IT], float outScale = 1.0f) {
   const int nPos = (NCHW_VAR & 4) ? (p.Wo < 0 ? IT : 0) : min(IT, p.Wo - w.ocol);
   float* __restrict__ dst = p.dst + (((size_t)w.panel * (p.Ho * p.Wo) + w.orow * p.Wo + w.ocol + (w.kq >> 1)) * p.Ct + w.li) * PANEL +
                             w.it * 16 + 4 * (w.kq & 1);
@@ -452,7 +454,10 @@ __device__ __forceinline__ void nchw_store(const DecParams& p, const NchwItem& w
             const int ti = tp * 2 + h;
             f32x4 v;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (0.0f < acc[ct][ti][e]) ? acc[ct][ti][e] : 0.0f;
+            for (int e = 0; e < 4; ++e) {
+              const float r = SCALED ? acc[ct][ti][e] * outScale : acc[ct][ti][e];
+              v[e] = (0.0f < r) ? r : 0.0f;
+            }
             *reinterpret_cast<f32x4*>(dst + ((size_t)tp * 2 * p.Ct + (w.cc * CT + ct) * 16) * PANEL + 8 * h) = v;
             __builtin_amdgcn_sched_barrier(0);
           }
@@ -463,9 +468,31 @@ __device__ __forceinline__ void nchw_store(const DecParams& p, const NchwItem& w
       if ((ti >> 1) * 2 + (w.kq >> 1) < nPos) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
-          *reinterpret_cast<f32x4*>(dst + ((size_t)(ti >> 1) * 2 * p.Ct + (w.cc * CT + ct) * 16) * PANEL + 8 * (ti & 1)) = acc[ct][ti];
+          *reinterpret_cast<f32x4*>(dst + ((size_t)(ti >> 1) * 2 * p.Ct + (w.cc * CT + ct) * 16) * PANEL + 8 * (ti & 1)) =
+              SCALED ? acc[ct][ti] * outScale : acc[ct][ti];
       }
   }
+}
+
+// The same rows for the images of `mask` only (bit i: image i of the item's sixteen), one float each: the fix-up launch behind
+// k_conv_dec_nchw_f16 leaves every other image's results as they are
+template <int CT, int IT>
+__device__ __forceinline__ void nchw_store_images(const DecParams& p, const NchwItem& w, const f32x4 (&acc)[CT][IT], unsigned mask) {
+  const int nPos = min(IT, p.Wo - w.ocol);
+  float* __restrict__ dst = p.dst + (((size_t)w.panel * (p.Ho * p.Wo) + w.orow * p.Wo + w.ocol + (w.kq >> 1)) * p.Ct + w.li) * PANEL +
+                            w.it * 16 + 4 * (w.kq & 1);
+#pragma unroll
+  for (int ti = 0; ti < IT; ++ti)
+    if ((ti >> 1) * 2 + (w.kq >> 1) < nPos) {
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if ((mask >> (8 * (ti & 1) + 4 * (w.kq & 1) + e)) & 1u) {
+            const float r = acc[ct][ti][e];
+            dst[((size_t)(ti >> 1) * 2 * p.Ct + (w.cc * CT + ct) * 16) * PANEL + 8 * (ti & 1) + e] = p.relu ? ((0.0f < r) ? r : 0.0f) : r;
+          }
+    }
 }
 
 // s_waitcnt vmcnt(N) that the operands of a step pass through (the compiler must not move their uses above it)
@@ -569,7 +596,8 @@ __global__ void k_decode_weights_nchw(const uint8_t* __restrict__ rows, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// k_conv_dec_nchw_split (QCNN_OPT_DEC_BF16SPLIT, default): the same layer at fp32 accuracy on the BF16 matrix pipe.  The
+// k_conv_dec_nchw_split (QCNN_OPT_DEC_BF16SPLIT = 1; the default, 2, is k_conv_dec_nchw_f16 further down): the same layer at fp32
+// accuracy on the BF16 matrix pipe.  The
 // f32 kernel above is bound by v_mfma_f32_16x16x4_f32 (32 cycles per 4 k: 1.42 of its 1.85 ms); gfx950 has no xf32, and its
 // bf16 rate is 16x the f32 one.  Every fp32 value splits EXACTLY into three bf16 pieces (round to nearest, remainder in
 // fp32: 8 + 8 + 8 significant bits), x = x1 + x2 + x3, w = w1 + w2 + w3, and the six cross terms down to order 2^-16,
@@ -623,6 +651,10 @@ __device__ __forceinline__ void split_wait(f32x4 (&x)[4][2]) {
 template <int N>
 __device__ __forceinline__ void split_wait(u32x4& w) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w) : "n"(N)); }
 
+// The per-launch guard region of k_conv_dec_nchw_f16 (p.guard): word 0 = p.epoch when the launch flagged anything (never
+// cleared: the next launch has another epoch), then from byte 16 one 16-bit image mask per item
+__device__ __forceinline__ uint16_t* nchw_guard_masks(const DecParams& p) { return reinterpret_cast<uint16_t*>(p.guard + 4); }
+
 // runs per kernel row of the run order (k_conv_dec_nchw_split<.., RUNS>), 0: the flat order; Kb of either order
 static inline int nchw_split_kb(int Cin, int knl, int nr) { return nr ? (Cin * knl * nr + 7) / 8 * 32 : (Cin * knl * knl + 31) / 32 * 32; }
 static inline size_t nchw_split_lds(int Kb, int Ct, int nr) {    // w1 / w2 + the offset table (one step of slack behind it)
@@ -634,15 +666,10 @@ static int nchw_split_runs(int Cin, int knl, int Ct) {
   return nchw_split_lds(nchw_split_kb(Cin, knl, nr), Ct, nr) <= 160 * 1024 ? nr : 0;
 }
 
-template <int CT, int IT, bool RUNS>
-__global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecParams p) {
-  static_assert(IT == 4 && CT == 6, "a product tile is 2 positions x 8 images, an item two pairs of positions x two image halves x 96 channels");
-  extern __shared__ __attribute__((aligned(16))) float ldsW[];          // [steps][S / 16][piece 2][64 lanes][8 bf16], then int [Kp + 32]
-                                                                        // (RUNS: int [Kp / 4 + 8], one per run)
-  const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
-  const int steps = p.Kp >> 5;                                          // Kp: Cin knl^2 padded to a multiple of 32
-  const int CTs = p.S >> 4;                                             // channel tiles of the layer
-  int* ldsOff = reinterpret_cast<int*>(ldsW + (size_t)p.Kp * p.S);
+// What the two split kernels (bf16 pieces below, fp16 pieces further down) share: both pieces of every code word in LDS, 4 bytes
+// per code word, and behind them the offset table of the k order — RUNS: one entry per run of 4 columns, else one per k
+template <bool RUNS>
+__device__ __forceinline__ void split_fill_lds(const DecParams& p, float* ldsW, int* ldsOff) {
   lds_fill<64 * NCHW_WAVES>(ldsW, p.wdec, (p.Kp * p.S) >> 2);          // w1, w2: 4 bytes per code word
   if constexpr (RUNS) {
     const int nr = (p.knl + 3) >> 2, nRuns = p.Cin * p.knl * nr;
@@ -653,6 +680,56 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
   } else {
     nchw_flat_offsets(p, ldsOff, p.Kp + 32);
   }
+}
+
+// the operand loads of step s (lane: k = 32 s + 8 kq + j; offT: the lane's part of the offset table).  RUNS: 2 x IT, one
+// dwordx4 per run (k = 4 run + e), else 8 x IT dwords
+template <int IT, bool RUNS>
+__device__ __forceinline__ void split_issue_x(const int* __restrict__ offT, int s, const int (&laneOffT)[IT], const uint32_t (&baseT)[IT],
+                                              i32x4_t rsrc4, f32x4 (&xr)[IT][2]) {
+  if constexpr (RUNS) {
+    typedef int i32x2_t __attribute__((ext_vector_type(2)));
+    const i32x2_t o = *reinterpret_cast<const i32x2_t*>(offT + 8 * s);
+#pragma unroll
+    for (int ti = 0; ti < IT; ++ti)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (NCHW_VAR & 1) {
+          float v;
+          asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(o[h]));
+          xr[ti][h] = f32x4{v, v, v, v};
+        } else
+        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(xr[ti][h]) : "v"(o[h] + laneOffT[ti]), "s"(rsrc4), "s"(baseT[ti]));
+      }
+  } else {
+    const i32x4_t o0 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s), o1 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s + 4);
+    const int ot[8] = {o0[0], o0[1], o0[2], o0[3], o1[0], o1[1], o1[2], o1[3]};
+#pragma unroll
+    for (int ti = 0; ti < IT; ++ti)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v;
+        if (NCHW_VAR & 1) asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(ot[j]));
+        else asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(ot[j] + laneOffT[ti]), "s"(rsrc4), "s"(baseT[ti]));
+        xr[ti][j >> 2][j & 3] = v;
+      }
+  }
+}
+
+// FIXUP (k_conv_dec_nchw_fixup): the launch behind k_conv_dec_nchw_f16 (further down).  It leaves at once unless that launch flagged an input value
+// outside the fp16 form's range (p.guard[0] == p.epoch); then it computes the flagged items — same items, same sums, same bits
+// as this kernel alone — and stores the flagged images' results only.
+template <int CT, int IT, bool RUNS, bool FIXUP>
+__device__ __forceinline__ void conv_dec_nchw_split(const DecParams& p, float* ldsW) {
+  static_assert(IT == 4 && CT == 6, "a product tile is 2 positions x 8 images, an item two pairs of positions x two image halves x 96 channels");
+  if constexpr (FIXUP) {
+    if (*p.guard != p.epoch) return;                                    // nothing flagged: no LDS fill, no item
+  }
+  const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
+  const int steps = p.Kp >> 5;                                          // Kp: Cin knl^2 padded to a multiple of 32
+  const int CTs = p.S >> 4;                                             // channel tiles of the layer
+  int* ldsOff = reinterpret_cast<int*>(ldsW + (size_t)p.Kp * p.S);
+  split_fill_lds<RUNS>(p, ldsW, ldsOff);
   __syncthreads();
   const NchwGrid g = nchw_grid<CT, IT>(p);
   const i32x4_t rsrc4 = raw_rsrc(p.src, (unsigned long long)p.nImages * g.imgBytes);
@@ -662,6 +739,11 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
   const i32x4_t rsrcW = raw_rsrc(p.wdec + (size_t)p.Kp * p.S, (uint32_t)p.Kp * p.S * 2u);
   const ItemRange ir = xcd_items<NCHW_WAVES, true>(g.nItems, wave);
   for (int item = ir.first; item < ir.end; item += ir.stride) {
+    unsigned fixMask = 0;
+    if constexpr (FIXUP) {
+      fixMask = uni(nchw_guard_masks(p)[item]);
+      if (!fixMask) continue;
+    }
     const NchwItem w = nchw_item<IT>(p, g, item, lane);
    auto body = [&](auto edgeTag) {
     int laneOffT[IT];
@@ -669,36 +751,7 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
     nchw_tile_bases<decltype(edgeTag)::value>(p, g, w, laneOffT, baseT);
     const int* __restrict__ offT = ldsOff + (RUNS ? 2 : 8) * w.kq;
     f32x4 xr[IT][2];                                                    // raw operands of the next step
-    // the operand loads of step s (lane: k = 32 s + 8 kq + j).  RUNS: 2 x IT, one dwordx4 per run (k = 4 run + e)
-    auto issue_x = [&, rsrc4](int s) {
-      if constexpr (RUNS) {
-        typedef int i32x2_t __attribute__((ext_vector_type(2)));
-        const i32x2_t o = *reinterpret_cast<const i32x2_t*>(offT + 8 * s);
-#pragma unroll
-        for (int ti = 0; ti < IT; ++ti)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            if (NCHW_VAR & 1) {
-              float v;
-              asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(o[h]));
-              xr[ti][h] = f32x4{v, v, v, v};
-            } else
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(xr[ti][h]) : "v"(o[h] + laneOffT[ti]), "s"(rsrc4), "s"(baseT[ti]));
-          }
-        return;
-      }
-      const i32x4_t o0 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s), o1 = *reinterpret_cast<const i32x4_t*>(offT + 32 * s + 4);
-      const int ot[8] = {o0[0], o0[1], o0[2], o0[3], o1[0], o1[1], o1[2], o1[3]};
-#pragma unroll
-      for (int ti = 0; ti < IT; ++ti)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float v;
-          if (NCHW_VAR & 1) asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "v"(ot[j]));
-          else asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(ot[j] + laneOffT[ti]), "s"(rsrc4), "s"(baseT[ti]));
-          xr[ti][j >> 2][j & 3] = v;
-        }
-    };
+    auto issue_x = [&, rsrc4](int s) { split_issue_x<IT, RUNS>(offT, s, laneOffT, baseT, rsrc4, xr); };
     u32x4 w3[CT];                                                       // w3 of (step, channel tile): one dwordx4 per lane
     const int w3Lane = lane * 16;
     auto issue_w3 = [&, rsrcW, w3Step](int s, int ct) {
@@ -757,10 +810,23 @@ __global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecPara
     split_wait<0>(xr);                                                  // nothing in flight into registers the stores may reuse
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) split_wait<0>(w3[ct]);
+    if constexpr (FIXUP) nchw_store_images(p, w, acc, fixMask); else
     nchw_store(p, w, acc);
    };
     if (w.edge) body(std::true_type{}); else body(std::false_type{});
   }
+}
+
+// ldsW: [steps][S / 16][piece 2][64 lanes][8 bf16], then int [Kp + 32] (RUNS: int [Kp / 4 + 8], one per run)
+template <int CT, int IT, bool RUNS>
+__global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_split(DecParams p) {
+  extern __shared__ __attribute__((aligned(16))) float ldsW[];
+  conv_dec_nchw_split<CT, IT, RUNS, false>(p, ldsW);
+}
+template <int CT, int IT, bool RUNS>
+__global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_fixup(DecParams p) {
+  extern __shared__ __attribute__((aligned(16))) float ldsW[];
+  conv_dec_nchw_split<CT, IT, RUNS, true>(p, ldsW);
 }
 
 __device__ __forceinline__ float bf16_hi(float x, uint16_t* h) {      // round to nearest even (finite x); returns the piece as fp32
@@ -797,6 +863,190 @@ __global__ void k_decode_weights_split(const uint8_t* __restrict__ rows, const f
     out[blk] = h1;
     out[blk + 512] = h2;
     out3[i] = h3;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// k_conv_dec_nchw_f16 (QCNN_OPT_DEC_BF16SPLIT = 2, default): the same layer with TWO fp16 pieces per operand and THREE cross
+// terms.  An fp16 piece has 11 significant bits: x1 = f16(Sx x), x2 = f16(Sx x - x1) (the remainder is exact in fp32) carry 22
+// bits of x, likewise w1, w2 of Sw w, and
+//     x2 w1, x1 w2, x1 w1                             (in that order: small terms first)
+// on v_mfma_f32_16x16x32_f16 — the bf16 instruction's 16 cycles — reproduce a product to 3 x 2^-22: the two split remainders
+// and the dropped x2 w2.  Half the matrix instructions of the bf16 form, no w3 plane (w1 / w2 as fp16 are the 4 bytes per code
+// word the LDS holds anyway), one split stage fewer.  fp16 has a narrow range, so both operands are scaled by exact powers
+// of two: Sx = QK_F16_SX for |x| <= QK_F16_XMAX, Sw per layer from max |w| (qk_f16_weight_scale; it stands in front of the
+// planes); the accumulators start from bias Sx Sw and the store multiplies by 1 / (Sx Sw), both exact.  Items, clamps, edge
+// handling, XCD split, LDS layout and k orders are the bf16 kernel's; the sum per output — bias, then per step the three terms
+// in fixed order — depends on nothing but the output.
+// RANGE GUARD: the API takes any float.  Every loaded value is tested with !(|x| <= QK_F16_XMAX) (NaN too); per product-tile row
+// = (position, image) the flags are reduced over k and the steps, rows of positions past the output row (they read another
+// image's columns) and of images past the batch are dropped, and the item's 16-bit image mask goes to p.guard (one writer per
+// entry, no atomics; word 0 = p.epoch when any mask is non-zero).  The fix-up launch (k_conv_dec_nchw_fixup) behind
+// this one recomputes the flagged (item, image) pairs with the bf16 form: their results are option 1's bits, every other
+// image's are untouched, and what an image gets never depends on its neighbours in the batch.
+// ------------------------------------------------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// Sx x = (x1 + x2) (1 + d), |d| <= 2^-22 (finite |x| <= QK_F16_XMAX; v_cvt_pk_f16_f32 rounds to nearest even)
+__device__ __forceinline__ void split_f16x8(const f32x4 (&x)[2], f16x8& h1, f16x8& h2) {
+  u32x4 p1, p2;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x2 sx = f32x2{x[q >> 1][2 * (q & 1)], x[q >> 1][2 * (q & 1) + 1]} * QK_F16_SX;
+    const f16x2 a = __builtin_convertvector(sx, f16x2);
+    const f32x2 r = sx - __builtin_convertvector(a, f32x2);
+    p1[q] = __builtin_bit_cast(unsigned, a);
+    p2[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+  }
+  h1 = __builtin_bit_cast(f16x8, p1); h2 = __builtin_bit_cast(f16x8, p2);
+}
+
+template <int CT, int IT, bool RUNS>
+__global__ __launch_bounds__(64 * NCHW_WAVES) void k_conv_dec_nchw_f16(DecParams p) {
+  static_assert(IT == 4 && CT == 6, "a product tile is 2 positions x 8 images, an item two pairs of positions x two image halves x 96 channels");
+  extern __shared__ __attribute__((aligned(16))) float ldsW[];          // [steps][S / 16][piece 2][64 lanes][8 fp16], then the offset table
+  const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
+  const int steps = p.Kp >> 5;
+  const int CTs = p.S >> 4;
+  int* ldsOff = reinterpret_cast<int*>(ldsW + (size_t)p.Kp * p.S);
+  split_fill_lds<RUNS>(p, ldsW, ldsOff);
+  __syncthreads();
+  const NchwGrid g = nchw_grid<CT, IT>(p);
+  const i32x4_t rsrc4 = raw_rsrc(p.src, (unsigned long long)p.nImages * g.imgBytes);
+  const float accScale = p.accScale, outScale = p.outScale;
+  uint32_t* const guard = p.guard;
+  uint16_t* const masks = nchw_guard_masks(p);
+  const uint32_t epoch = p.epoch;
+  const ItemRange ir = xcd_items<NCHW_WAVES, true>(g.nItems, wave);
+  for (int item = ir.first; item < ir.end; item += ir.stride) {
+    const NchwItem w = nchw_item<IT>(p, g, item, lane);
+   auto body = [&](auto edgeTag) {
+    unsigned long long bad[IT] = {0, 0, 0, 0};                          // per image tile: the lanes (rows x k quarters) that met a value out of range
+    int laneOffT[IT];
+    uint32_t baseT[IT];
+    nchw_tile_bases<decltype(edgeTag)::value>(p, g, w, laneOffT, baseT);
+    const int* __restrict__ offT = ldsOff + (RUNS ? 2 : 8) * w.kq;
+    f32x4 xr[IT][2];                                                    // raw operands of the next step
+    auto issue_x = [&, rsrc4](int s) { split_issue_x<IT, RUNS>(offT, s, laneOffT, baseT, rsrc4, xr); };
+    f32x4 acc[CT][IT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      const float b1 = p.bias[(w.cc * CT + ct) * 16 + w.li] * accScale;
+#pragma unroll
+      for (int ti = 0; ti < IT; ++ti) acc[ct][ti] = f32x4{b1, b1, b1, b1};
+    }
+    const u32x4* __restrict__ wl = reinterpret_cast<const u32x4*>(ldsW) + (size_t)(w.cc * CT) * 128 + lane;
+    const int wStep = CTs * 128;                                        // u32x4 per step
+    issue_x(0);
+    // The only loads in flight into registers are the operands of ONE step: step s waits for all of them (the previous
+    // item's stores may still be on their way, which only makes the first wait stricter), splits them and issues step
+    // s + 1's into the same registers, under its 72 matrix instructions
+    int s = 0;
+    do {
+      u32x4 bw[2][2];
+      bw[0][0] = wl[0]; bw[0][1] = wl[64];
+      split_wait<0>(xr);
+      f16x8 a1[IT], a2[IT];
+#pragma unroll
+      for (int ti = 0; ti < IT; ++ti) {
+        if (NCHW_VAR & 8) {
+          a1[ti] = __builtin_bit_cast(f16x8, xr[ti][0]);
+          a2[ti] = a1[ti];
+        } else {
+          bool out = false;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) out |= !(__builtin_fabsf(xr[ti][j >> 2][j & 3]) <= QK_F16_XMAX);
+          bad[ti] |= __builtin_amdgcn_ballot_w64(out);
+          split_f16x8(xr[ti], a1[ti], a2[ti]);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      issue_x(s + 1);                                                   // (the last step: the window's last element again, never used)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        if (ct + 1 < CT) { bw[(ct + 1) & 1][0] = wl[(ct + 1) * 128]; bw[(ct + 1) & 1][1] = wl[(ct + 1) * 128 + 64]; }
+        const f16x8 b1 = __builtin_bit_cast(f16x8, bw[ct & 1][0]), b2 = __builtin_bit_cast(f16x8, bw[ct & 1][1]);
+#define SPLIT_TERM(A, B)                                                                                               \
+  _Pragma("unroll") for (int ti = 0; ti < IT; ++ti)                                                                    \
+    if (NCHW_VAR & 2) asm volatile("" : "+v"(acc[ct][ti]) : "v"(A[ti]), "v"(B)); else                                  \
+    acc[ct][ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[ti], B, acc[ct][ti], 0, 0, 0);
+        SPLIT_TERM(a2, b1) SPLIT_TERM(a1, b2) SPLIT_TERM(a1, b1)
+#undef SPLIT_TERM
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      wl += wStep;
+    } while (++s < steps);
+    split_wait<0>(xr);                                                  // nothing in flight into registers the stores may reuse
+    nchw_store<CT, IT, true>(p, w, acc, outScale);
+    // the item's image mask: lane (li, kq) of tile ti is image 8 (ti & 1) + (li & 7) at position 2 (ti >> 1) + (li >> 3)
+    unsigned mask = 0;
+#pragma unroll
+    for (int ti = 0; ti < IT; ++ti) {
+      const unsigned long long m = bad[ti] & __builtin_amdgcn_ballot_w64(w.ocol + 2 * (ti >> 1) + (w.li >> 3) < p.Wo);
+      unsigned f = (unsigned)m | (unsigned)(m >> 32);
+      f |= f >> 16;
+      mask |= ((f | (f >> 8)) & 0xffu) << (8 * (ti & 1));
+    }
+    const int liveImgs = p.nImages - (int)w.img0;                       // a ragged last panel: image tiles past the batch
+    mask &= liveImgs >= 16 ? 0xffffu : liveImgs > 0 ? (1u << liveImgs) - 1u : 0u;
+    if (lane == 0) {
+      masks[item] = (uint16_t)mask;
+      if (mask) *guard = epoch;
+    }
+   };
+    if (w.edge) body(std::true_type{}); else body(std::false_type{});
+  }
+}
+
+// The layer's scale in front of its fp16 planes: out[0] = Sw (qk_f16_weight_scale; 0: the layer keeps the bf16 form), from the
+// largest |code word| any assignment of the layer names and the largest |bias|.  One workgroup, a fixed reduction tree.
+__global__ __launch_bounds__(1024) void k_f16_weight_scale(const uint8_t* __restrict__ rows, const float* __restrict__ ctrd,
+                                                           const float* __restrict__ bias, float* __restrict__ out, QkSlots sl,
+                                                           int knl, int Cin, int K, int Ct) {
+  __shared__ uint32_t red[2][1024];
+  uint32_t mw = 0, mb = 0;
+  const int total = Cin * knl * knl * Ct;
+  for (int i = threadIdx.x; i < total; i += 1024) {
+    const int ch = i % Ct, k = i / Ct;
+    mw = max(mw, __builtin_bit_cast(uint32_t, code_word(rows, ctrd, sl, knl, K, k / (knl * knl), (k / knl) % knl, k % knl, ch)) & 0x7fffffffu);
+  }
+  for (int i = threadIdx.x; i < Ct; i += 1024) mb = max(mb, __builtin_bit_cast(uint32_t, bias[i]) & 0x7fffffffu);
+  red[0][threadIdx.x] = mw; red[1][threadIdx.x] = mb;
+  __syncthreads();
+  for (int n = 512; n > 0; n >>= 1) {
+    if ((int)threadIdx.x < n) {
+      red[0][threadIdx.x] = max(red[0][threadIdx.x], red[0][threadIdx.x + n]);
+      red[1][threadIdx.x] = max(red[1][threadIdx.x], red[1][threadIdx.x + n]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = qk_f16_weight_scale(red[0][0], red[1][0]);
+}
+
+// The fp16 planes of k_conv_dec_nchw_f16: w1 = f16(Sw w), w2 = f16(Sw w - w1) in k_decode_weights_split's
+// [step][S / 16][piece][64 lanes][8] order (nr as there); scale[0] = Sw, 0: zeros (the layer is not eligible)
+__global__ void k_decode_weights_f16(const uint8_t* __restrict__ rows, const float* __restrict__ ctrd, const float* __restrict__ scale,
+                                     uint16_t* __restrict__ out, QkSlots sl, int knl, int Cin, int K, int Ct, int Kb, int S, int nr) {
+  const int total = Kb * S, CTs = S / 16;
+  const float Sw = scale[0];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int j = i & 7, ln = (i >> 3) & 63, tile = (i >> 9) % CTs, step = (i >> 9) / CTs;
+    const int ch = 16 * tile + (ln & 15), k = 32 * step + 8 * (ln >> 4) + j;
+    float w = 0.0f;
+    int kw = k % knl, kh = (k / knl) % knl, c = k / (knl * knl);
+    bool live = k < Cin * knl * knl;
+    if (nr) {
+      const int r = k >> 2, ri = r % nr;
+      kw = min(4 * ri, knl - 4) + (k & 3); kh = (r / nr) % knl; c = r / (nr * knl);
+      live = r < Cin * knl * nr && kw >= 4 * ri;
+    }
+    if (ch < Ct && live && Sw != 0.0f) w = code_word(rows, ctrd, sl, knl, K, c, kh, kw, ch) * Sw;
+    const _Float16 h1 = (_Float16)w, h2 = (_Float16)(w - (float)h1);
+    const size_t blk = (size_t)(step * CTs + tile) * 2 * 512 + ln * 8 + j;
+    out[blk] = __builtin_bit_cast(uint16_t, h1);
+    out[blk + 512] = __builtin_bit_cast(uint16_t, h2);
   }
 }
 
@@ -1033,4 +1283,36 @@ hipError_t qk_conv_dec_nchw_split(const DecParams& p, hipStream_t st) {
   const int nr = nchw_split_runs(p.Cin, p.knl, p.Ct);         // the order qk_decode_weights_split wrote
   if (p.Kp != nchw_split_kb(p.Cin, p.knl, nr)) return hipErrorInvalidValue;
   return launch_nchw(nr ? k_conv_dec_nchw_split<6, 4, true> : k_conv_dec_nchw_split<6, 4, false>, nchw_split_lds(p.Kp, p.S, nr), p, st);
+}
+
+size_t qk_conv_dec_nchw_f16_bytes(int Kb, int Ct) { return QK_F16_PLANES + (size_t)Kb * Ct * 4; }
+
+size_t qk_conv_dec_nchw_f16_guard_bytes(int Ho, int Wo, int Ct, int panels) {   // word + slack, then a mask per item of `panels` full panels
+  return 16 + (size_t)panels * Ho * ((Wo + 3) / 4) * (QCNN_PANEL / 16) * (Ct / 96) * sizeof(uint16_t);
+}
+
+hipError_t qk_decode_weights_f16(const uint8_t* rows, const float* ctrd, const float* bias, void* out, const QkSlots& sl, int knl,
+                                 int Cin, int K, int Ct, int Kb, hipStream_t st) {
+  const int total = Kb * Ct;
+  const int nr = nchw_split_runs(Cin, knl, Ct);
+  if (Kb != nchw_split_kb(Cin, knl, nr)) return hipErrorInvalidValue;
+  float* scale = static_cast<float*>(out);
+  hipLaunchKernelGGL(k_f16_weight_scale, dim3(1), dim3(1024), 0, st, rows, ctrd, bias, scale, sl, knl, Cin, K, Ct);
+  hipLaunchKernelGGL(k_decode_weights_f16, dim3((total + 255) / 256), dim3(256), 0, st, rows, ctrd, scale,
+                     reinterpret_cast<uint16_t*>(static_cast<char*>(out) + QK_F16_PLANES), sl, knl, Cin, K, Ct, Kb, Ct, nr);
+  return hipGetLastError();
+}
+
+// p: as for qk_conv_dec_nchw_split, with p.wdec = the fp16 planes (behind the scale), p.accScale = Sx Sw, p.outScale = its inverse,
+// p.guard / p.epoch = this launch's guard region and a number no earlier launch on that region carried; wBf16 = the planes of
+// qk_decode_weights_split for the fix-up launch
+hipError_t qk_conv_dec_nchw_f16(const DecParams& p, const float* wBf16, hipStream_t st) {
+  const int nr = nchw_split_runs(p.Cin, p.knl, p.Ct);
+  if (p.Kp != nchw_split_kb(p.Cin, p.knl, nr) || !p.guard || !p.epoch) return hipErrorInvalidValue;
+  const size_t shm = nchw_split_lds(p.Kp, p.S, nr);
+  const hipError_t e = launch_nchw(nr ? k_conv_dec_nchw_f16<6, 4, true> : k_conv_dec_nchw_f16<6, 4, false>, shm, p, st);
+  if (e != hipSuccess || (NCHW_VAR & 32)) return e;
+  DecParams q = p;
+  q.wdec = wBf16;
+  return launch_nchw(nr ? k_conv_dec_nchw_fixup<6, 4, true> : k_conv_dec_nchw_fixup<6, 4, false>, shm, q, st);
 }

@@ -46,6 +46,10 @@ struct LayerShape {
   int cbnBits = 0;                                             // bits per assignment of the T_CBN span
   size_t offDecN = 0; int decNV = 0;                          // first layer: the same code words in k_conv_dec_nchw's order; decNV: its padded k (0: not eligible)
   size_t offDecB = 0; int decBK = 0;                          // ... split into three bf16 pieces for k_conv_dec_nchw_split; decBK: its padded k (0: not eligible)
+  size_t offDecH = 0;                                          // ... as two fp16 pieces behind their scale Sw for k_conv_dec_nchw_f16 (same decBK)
+  int decF16 = -1; float decSw = 0.0f;                         // ... that scale as the decoder left it in the arena: -1 not read back yet (an upload, a
+                                                               // broadcast arena), 0 the layer keeps the bf16 form (Sw = 0), 1 eligible
+  int lastForm = 0;                                            // decoded first layer: the form of the last launch (0 f32, 1 bf16 pieces, 2 fp16 pieces)
   size_t offDec = 0; int decKp = 0, decS = 0;                  // decoded code words (qcnn_decoded.hip): conv layer with one sub-space of
                                                                // <= 4 dims (decKp > 0), FC layer with one-dim sub-spaces (decKp = -1); 0: not eligible
   bool hasDmap = false;
@@ -86,7 +90,8 @@ struct QcnnCtx {
   int smallBatch = 1;                // QCNN_OPT_SMALL_BATCH: few-image kernels for batches <= kSmallBatchMax
   int hostChunk = 2;                 // QCNN_OPT_HOST_CHUNK: panels per chunk of a large qcnn_forward_host batch (0: one launch)
   int directDec = 1;                 // QCNN_OPT_DIRECT_DEC: a decoded first layer reads the NCHW input in place (k_conv_dec_nchw) on the fast path
-  int decSplit = 1;                  // QCNN_OPT_DEC_BF16SPLIT: ... with its products as fp32-accurate split-bf16 MFMAs (k_conv_dec_nchw_split)
+  int decSplit = 2;                  // QCNN_OPT_DEC_BF16SPLIT: ... with its products as fp32-accurate split MFMAs: 1 three bf16 pieces
+                                     // (k_conv_dec_nchw_split), 2 two fp16 pieces where the layer's scale allows (k_conv_dec_nchw_f16), else as 1
   int packedFc = 0;                  // QCNN_OPT_PACKED_FC (default off: measured 0.056 against 0.035 ms for AlexNet fc6 at one image): the few-image FC kernel reads the bit-packed assignment stream in place
   int half8 = 1;                     // QCNN_OPT_HALF8: half-panel eight-wave workgroups where predicted faster (2: whenever eligible)
   int sym8 = 1;                      // QCNN_OPT_SYM8: eight-wave symmetric workgroups where predicted faster (2: whenever eligible)
@@ -122,6 +127,13 @@ struct QcnnCtx {
   hipEvent_t evCopied[2] = {nullptr, nullptr}, evFreed[2] = {nullptr, nullptr}, evDone[2] = {nullptr, nullptr};
   bool freedValid[2] = {false, false};
   std::vector<hipEvent_t> evChunk;   // chunked single batch (qcnn_forward_host): "chunk k is on the device"
+  // k_conv_dec_nchw_f16's range guard: one region per sub-batch stream (word + a 16-bit image mask per item, sized for maxPanels),
+  // allocated at the first launch, freed with the model; decEpoch: the number the region's last launch carried, decGuardItems: its
+  // items (0: the sub-batch did not run the fp16 form in the last forward) — what qcnn_get_layer_dec_form reads back
+  uint32_t* decGuard = nullptr;
+  size_t decGuardBytes = 0;          // per region
+  uint32_t decEpoch[qcnn_engine::kMaxStreams] = {0};
+  int decGuardItems[qcnn_engine::kMaxStreams] = {0};
   float* fcFlat = nullptr;           // first FC layer's input in consumption order
   float* fcPartial = nullptr;        // split-M partial sums of the FC layers
   float* convPartial = nullptr;      // partial sums of split conv tiles (kConvPartialFloats)
@@ -230,6 +242,7 @@ int ensure_stage(QcnnCtx* c, size_t elems = 0);          // stageIn / stageOut /
 int ensure_pipeline(QcnnCtx* c);                         // ... + events, pinned results and stageIn1 of the pipelined float path
 int ensure_u8_stream(QcnnCtx* c, size_t srcBytes);       // ... + what the 8-bit stream owns (QcnnCtx::U8Stream)
 float* ensure_conv_partial(QcnnCtx* c);                  // convPartial; nullptr: the device has no room for it (no error)
+uint32_t* ensure_dec_guard(QcnnCtx* c, int sub);         // decGuard's region of sub-batch `sub`; nullptr after fail()
 int views_scratch(QcnnCtx* c, int n, bool wantMean);     // viewMean for n images
 QcnnCtx::SrcStage* stage_take(QcnnCtx* c, size_t n, size_t each);   // the next descriptor staging set; nullptr after fail()
 

@@ -64,6 +64,7 @@ int plan_arena(QcnnCtx* c) {
         s.offDecN = off; off = align_up(off + sizeof(float) * (size_t)s.decNV * Ct, 256);
         if (qk_conv_dec_nchw_split_shape(c->dims[l].c, d.grpCnt, s.M, Ct, d.knlSiz, d.padSiz, &s.decBK)) {   // derived like the copy above
           s.offDecB = off; off = align_up(off + 6 * (size_t)s.decBK * Ct, 256);                           // w1, w2, w3: 2 bytes each
+          s.offDecH = off; off = align_up(off + qk_conv_dec_nchw_f16_bytes(s.decBK, Ct), 256);            // Sw, then w1, w2 as fp16
         }
       }
     } else if (d.type == QCNN_FCNT && !s.hasDmap && qk_fc_dec_shape((int)fm_elems(c, l), s.M, s.Cs, Ct, &s.decS)) {
@@ -115,6 +116,9 @@ void free_model(QcnnCtx* c) {
   c->convPartial = nullptr; c->noConvPartial = false;
   if (c->fcFlat) (void)hipFree(c->fcFlat);
   c->fcFlat = nullptr;
+  if (c->decGuard) (void)hipFree(c->decGuard);
+  c->decGuard = nullptr; c->decGuardBytes = 0;
+  for (int k = 0; k < kMaxStreams; ++k) { c->decEpoch[k] = 0; c->decGuardItems[k] = 0; }
   c->stageIn = c->stageOut = nullptr; c->stageTop5 = nullptr; c->stageElems = 0;
   c->fcPartial = nullptr; c->fcPartialElems = 0;
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -239,6 +243,24 @@ float* ensure_conv_partial(QcnnCtx* c) {
     c->convPartial = nullptr; c->noConvPartial = true;
   }
   return c->convPartial;
+}
+
+// Guard regions of the first layer's fp16 form (k_conv_dec_nchw_f16): kMaxStreams regions, each for the items of maxPanels panels,
+// zeroed once (word 0 of a region must not hold a launch's number before that launch ran)
+uint32_t* ensure_dec_guard(QcnnCtx* c, int sub) {
+  if (!c->decGuard) {
+    const size_t bytes = align_up(qk_conv_dec_nchw_f16_guard_bytes(c->dims[1].h, c->dims[1].w, c->dims[1].c, c->maxPanels), 256);
+    hipError_t e = hipMalloc(&c->decGuard, bytes * kMaxStreams);
+    if (e == hipSuccess) e = hipMemset(c->decGuard, 0, bytes * kMaxStreams);
+    if (e != hipSuccess) {
+      if (c->decGuard) (void)hipFree(c->decGuard);
+      c->decGuard = nullptr;
+      fail(c, "range-guard regions of the first layer: %s", hipGetErrorString(e));
+      return nullptr;
+    }
+    c->decGuardBytes = bytes;
+  }
+  return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c->decGuard) + c->decGuardBytes * sub);
 }
 
 // The multi-view calls, BEFORE their pack kernel is launched: the map of the averaged rows is large enough for n images.
@@ -373,7 +395,7 @@ int qcnn_set_option(QcnnCtx* c, int option, int value) {
     case QCNN_OPT_SYM8: if (value < 0 || value > 3) return fail(c, "QCNN_OPT_SYM8 must be 0 (off), 1 (planner), 2 (forced tile form) or 3 (forced sliding form)"); c->sym8 = value; return 0;
     case QCNN_OPT_PACKED_FC: c->packedFc = value ? 1 : 0; return 0;
     case QCNN_OPT_DIRECT_DEC: c->directDec = value ? 1 : 0; return 0;
-    case QCNN_OPT_DEC_BF16SPLIT: c->decSplit = value ? 1 : 0; return 0;
+    case QCNN_OPT_DEC_BF16SPLIT: if (value < 0 || value > 2) return fail(c, "QCNN_OPT_DEC_BF16SPLIT must be 0 (f32), 1 (three bf16 pieces) or 2 (two fp16 pieces)"); c->decSplit = value; return 0;
     case QCNN_OPT_SYM: if (value < 0 || value > 2) return fail(c, "QCNN_OPT_SYM must be 0 (off), 1 (planner) or 2 (forced)"); c->sym = value; return 0;
     case QCNN_OPT_SLIDE: if (value < 0 || value > 2) return fail(c, "QCNN_OPT_SLIDE must be 0 (off), 1 (planner) or 2 (forced)"); c->slide = value; return 0;
     case QCNN_OPT_HOST_CHUNK:

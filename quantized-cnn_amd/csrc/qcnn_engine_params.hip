@@ -148,7 +148,7 @@ int upload_packed_assignments(QcnnCtx* c, int layer, const uint8_t* asmt_file) {
 // assignment rows of a layer (already in the arena, same stream) -> its decoded code words and every table of kTables it has
 hipError_t build_program(QcnnCtx* c, int layer) {
   const QcnnLayerDesc& d = c->layers[layer];
-  const LayerShape& s = c->shapes[layer];
+  LayerShape& s = c->shapes[layer];
   const TableGeom g = table_geom(c, layer);
   const QkSlots& sl = g.sl;
   const uint8_t* rows = arena_at<const uint8_t>(c, s.offAsmt);
@@ -163,6 +163,9 @@ hipError_t build_program(QcnnCtx* c, int layer) {
     e = qk_decode_weights_nchw(rows, ctrd, arena_at<float>(c, s.offDecN), sl, d.knlSiz, Cin, s.K, Ct, s.decNV, Ct, c->stream);
   if (e == hipSuccess && s.decKp > 0 && s.decNV && s.decBK)
     e = qk_decode_weights_split(rows, ctrd, arena_at<uint16_t>(c, s.offDecB), sl, d.knlSiz, Cin, s.K, Ct, s.decBK, c->stream);
+  if (e == hipSuccess && s.decKp > 0 && s.decNV && s.decBK)      // ... and as two fp16 pieces behind the scale the decoder chooses
+    e = qk_decode_weights_f16(rows, ctrd, arena_at<const float>(c, s.offBias), arena_at<void>(c, s.offDecH), sl, d.knlSiz, Cin, s.K, Ct, s.decBK, c->stream);
+  s.decF16 = -1;                                                 // read back by the first launch that asks (launch_conv)
   for (int k = 0; k < T_COUNT && e == hipSuccess; ++k)
     if (s.tab[k].bytes && kTables[k].build) e = kTables[k].build(g, rows, arena_at<uint16_t>(c, s.tab[k].off), c->stream, 0);
   return e;
@@ -376,6 +379,7 @@ int qcnn_model_mark_loaded(QcnnCtx* c) {
     if (c->aux[k]) HIP_TRY(c, hipStreamSynchronize(c->aux[k]));
   for (int l = 0; l < c->L; ++l) {
     drop_f16_programs(c->shapes[l]);
+    c->shapes[l].decF16 = -1;                     // the first layer's fp16 scale: whatever the arena holds now
     if (c->shapes[l].K > 0 || c->shapes[l].dense) c->shapes[l].loaded = true;
   }
   return 0;

@@ -82,10 +82,31 @@ int launch_conv(QcnnCtx* c, int l, const Launch& L) {
     q.Kr = d.knlSiz * a.c; q.Kp = s.decKp; q.S = s.decS;
     if (inNchw) { q.Kr = d.knlSiz * d.knlSiz * a.c; q.Kp = s.decNV; q.S = b.c; }
     q.live = L.live;
+    q.accScale = q.outScale = 1.0f; q.guard = nullptr; q.epoch = 0;
     s.lastFrom = -3; s.lastZ = inNchw ? 2 : 1;        // reported by qcnn_get_layer_split as (-3, 1), NCHW in place: (-3, 2)
-    const bool splitBf16 = inNchw && c->decSplit && s.decBK > 0;   // fp32-accurate split-bf16 products (QCNN_OPT_DEC_BF16SPLIT)
+    const bool splitBf16 = inNchw && c->decSplit && s.decBK > 0;   // fp32-accurate split products (QCNN_OPT_DEC_BF16SPLIT)
     if (splitBf16) { q.Kp = s.decBK; q.wdec = arena_at<const float>(c, s.offDecB); }
-    const hipError_t e = splitBf16 ? qk_conv_dec_nchw_split(q, st) : inNchw ? qk_conv_dec_nchw(q, st) : qk_conv_dec(q, st);
+    // ... as two fp16 pieces (value 2) when the decoder found a scale for the layer: Sw stands in front of the planes, read back
+    // once per upload (uploads end with a synchronised stream; the arena does not change between them)
+    if (splitBf16 && c->decSplit == 2 && s.decF16 < 0) {
+      HIP_TRY(c, hipMemcpy(&s.decSw, arena_at<const float>(c, s.offDecH), sizeof(float), hipMemcpyDeviceToHost));
+      s.decF16 = s.decSw > 0.0f ? 1 : 0;
+    }
+    if (L.sub == 0) for (int& n : c->decGuardItems) n = 0;    // (what qcnn_get_layer_dec_form counts: this forward's launches)
+    hipError_t e;
+    if (splitBf16 && c->decSplit == 2 && s.decF16 == 1) {
+      if (!(q.guard = ensure_dec_guard(c, L.sub))) return 1;
+      if (++c->decEpoch[L.sub] == 0) c->decEpoch[L.sub] = 1;   // never 0 (the regions start zeroed); the word is compared, never cleared
+      q.epoch = c->decEpoch[L.sub];
+      q.accScale = QK_F16_SX * s.decSw; q.outScale = 1.0f / q.accScale;
+      q.wdec = reinterpret_cast<const float*>(arena_at<const char>(c, s.offDecH) + QK_F16_PLANES);
+      e = qk_conv_dec_nchw_f16(q, arena_at<const float>(c, s.offDecB), st);
+      if (e == hipSuccess) c->decGuardItems[L.sub] = q.panels * b.h * ((b.w + 3) / 4) * ((q.live + 15) / 16) * (b.c / 96);
+      s.lastForm = 2;
+    } else {
+      e = splitBf16 ? qk_conv_dec_nchw_split(q, st) : inNchw ? qk_conv_dec_nchw(q, st) : qk_conv_dec(q, st);
+      s.lastForm = splitBf16 ? 1 : 0;
+    }
     if (e != hipErrorInvalidValue) return launched(c, l, e);   // (a map beyond the kernel's 32-bit byte offsets: the table kernel below)
   }
   ConvParams p;
@@ -555,6 +576,32 @@ int qcnn_get_layer_split(QcnnCtx* c, int layer, int* tiles_unsplit, int* slices)
   const LayerShape& s = c->shapes[layer];
   if (tiles_unsplit) *tiles_unsplit = s.lastFrom;
   if (slices) *slices = s.lastZ;
+  return 0;
+}
+
+int qcnn_get_layer_dec_form(QcnnCtx* c, int layer, int* form, long long* fallback_pairs) {
+  if (layer < 0 || layer >= c->L) return fail(c, "layer %d out of range", layer);
+  const LayerShape& s = c->shapes[layer];
+  const bool inPlace = s.lastFrom == -3 && s.lastZ == 2;
+  if (form) *form = inPlace ? s.lastForm : -1;
+  if (!fallback_pairs) return 0;
+  *fallback_pairs = 0;
+  if (!inPlace || s.lastForm != 2 || !c->decGuard) return 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < kMaxStreams - 1; ++k)
+    if (c->aux[k]) HIP_TRY(c, hipStreamSynchronize(c->aux[k]));
+  std::vector<uint16_t> host;
+  for (int k = 0; k < kMaxStreams; ++k) {
+    const int items = c->decGuardItems[k];
+    if (!items) continue;
+    host.resize(8 + (size_t)items);                       // the word and its slack, then the masks
+    HIP_TRY(c, hipMemcpy(host.data(), reinterpret_cast<const char*>(c->decGuard) + c->decGuardBytes * k, host.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    uint32_t word = 0;
+    memcpy(&word, host.data(), sizeof(word));
+    if (word != c->decEpoch[k]) continue;                 // this launch flagged nothing: its fix-up left at once
+    for (int i = 0; i < items; ++i) *fallback_pairs += __builtin_popcount(host[8 + (size_t)i]);
+  }
   return 0;
 }
 

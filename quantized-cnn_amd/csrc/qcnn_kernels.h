@@ -384,6 +384,9 @@ struct DecParams {
   int knl, stride, pad;
   int Kr, Kp, S;         // knl * Cin, the same rounded up to a multiple of 4, channel stride of wdec
   int relu, panels, live;
+  float accScale, outScale;   // qk_conv_dec_nchw_f16: Sx Sw (the sums' unit is its inverse) and 1 / (Sx Sw)
+  uint32_t* guard;       // ... its guard region of this launch: word 0, then from byte 16 one 16-bit image mask per item
+  uint32_t epoch;        // ... what word 0 holds when THIS launch flagged a value out of range (never 0)
 };
 bool qk_conv_dec_shape(int Cin, int grp, int M, int Ct, int knl, int* Kp, int* S);   // is the layer eligible (and its wdec shape)
 hipError_t qk_decode_weights(const uint8_t* rows, const float* ctrd, float* out, const QkSlots& sl, int knl, int Cin, int K,
@@ -403,6 +406,31 @@ bool qk_conv_dec_nchw_split_shape(int Cin, int grp, int M, int Ct, int knl, int 
 hipError_t qk_decode_weights_split(const uint8_t* rows, const float* ctrd, uint16_t* out, const QkSlots& sl, int knl, int Cin, int K,
                                    int Ct, int Kb, hipStream_t st);
 hipError_t qk_conv_dec_nchw_split(const DecParams& p, hipStream_t st);   // p.Kp = Kb, p.S = Ct
+// Its two-piece fp16 form (QCNN_OPT_DEC_BF16SPLIT = 2): x1 = f16(Sx x), x2 = f16(Sx x - x1), w1 / w2 likewise of Sw w, three cross
+// terms x2 w1, x1 w2, x1 w1 per step; same Kb, k order, items and LDS size as the bf16 form.  Both scales are exact powers of
+// two: Sx = QK_F16_SX, and inputs with !(|x| <= QK_F16_XMAX) (NaN, Inf) are caught per (item, image) and recomputed by a fix-up
+// launch in the bf16 form (their bits are that form's); Sw = qk_f16_weight_scale of the layer's largest |code word| and |bias|
+// puts the largest w1 into [2^13, 2^14].  Arena: [QK_F16_PLANES bytes: float Sw, 0 = the layer keeps the bf16 form][w1 / w2 fp16
+// in qk_decode_weights_split's order, Kb x Ct x 4 bytes].
+#define QK_F16_SX 64.0f
+#define QK_F16_XMAX 1023.0f      // QK_F16_SX x QK_F16_XMAX = 65472 <= 65504, the largest fp16
+#define QK_F16_PLANES 256
+// maxW / maxBias: the bit patterns of the largest |code word| and |bias|.  e = floor(log2 max |w|): Sw = 2^(13 - e) for normal,
+// finite max |w| with -107 <= e <= 19 — 1 <= Sx Sw <= 2^126, so bias Sx Sw and the store's 1 / (Sx Sw) are exact — and a finite
+// bias with |bias| Sx Sw <= 2^100 (the accumulators hold it beside sums below 2^40); else 0
+__host__ __device__ inline float qk_f16_weight_scale(uint32_t maxW, uint32_t maxBias) {
+  const int e = (int)(maxW >> 23) - 127;
+  if (maxW >= 0x7f800000u || maxW < 0x00800000u || e < -107 || e > 19 || maxBias >= 0x7f800000u) return 0.0f;
+  const uint32_t swBits = (uint32_t)(13 - e + 127) << 23, limBits = (uint32_t)(100 + 127) << 23;
+  float Sw = 0.0f, b = 0.0f, lim = 0.0f;
+  __builtin_memcpy(&Sw, &swBits, 4); __builtin_memcpy(&b, &maxBias, 4); __builtin_memcpy(&lim, &limBits, 4);
+  return b * (QK_F16_SX * Sw) <= lim ? Sw : 0.0f;
+}
+size_t qk_conv_dec_nchw_f16_bytes(int Kb, int Ct);
+size_t qk_conv_dec_nchw_f16_guard_bytes(int Ho, int Wo, int Ct, int panels);
+hipError_t qk_decode_weights_f16(const uint8_t* rows, const float* ctrd, const float* bias, void* out, const QkSlots& sl, int knl,
+                                 int Cin, int K, int Ct, int Kb, hipStream_t st);
+hipError_t qk_conv_dec_nchw_f16(const DecParams& p, const float* wBf16, hipStream_t st);
 // FC layer with one-dim sub-spaces through its decoded code words (qcnn_decoded.hip).  wdec: [D][S], S = Ct rounded up to 64
 struct FcDecParams {
   const float* src;      // [panels][D][128]

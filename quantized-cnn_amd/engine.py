@@ -626,6 +626,14 @@ class QcnnEngine:
         self._chk(self.lib.qcnn_get_layer_split(self.h, l, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def layer_dec_form(self, l: int):
+        """(form, fallback pairs) of the last launch of a first conv layer read in place: form 0 = f32 matrix instructions,
+        1 = three bf16 pieces, 2 = two fp16 pieces (OPT_DEC_BF16SPLIT), -1 = another kernel ran; fallback pairs = the (work
+        item, image) pairs form 2's fix-up launch recomputed in form 1 for input values outside its range.  Synchronises."""
+        form, pairs = C.c_int(0), C.c_longlong(0)
+        self._chk(self.lib.qcnn_get_layer_dec_form(self.h, l, C.byref(form), C.byref(pairs)))
+        return form.value, pairs.value
+
     def layer_segments(self, l: int):
         """Row-segment boundaries of the sliding kernel's last launch of conv layer l ([] = the tile kernel ran)."""
         seg = (C.c_int * 9)()

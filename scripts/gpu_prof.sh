@@ -1,5 +1,6 @@
-# rocprofv3 passes for profiles/: kernel trace + stats, then PMC counters in their own runs (CSV output).
-set -x
+# rocprofv3 passes for profiles/: kernel trace + stats, then PMC counters in their own runs (CSV output).  A pass that fails or
+# runs into its time limit ends the script: nothing more is started on the GPU behind it.
+set -ex
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
@@ -15,4 +16,4 @@ pmc pmc5 GRBM_GUI_ACTIVE GRBM_COUNT
 find $OUT -name "*.db" -delete
 find $OUT -type f -size +8M -delete
 find $OUT -type f | xargs ls -la
-tail -3 $OUT/*.err
+tail -n 3 $OUT/*.err
