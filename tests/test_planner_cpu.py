@@ -3,7 +3,9 @@ build/libqcnn_planner_cpu.so — the same functions libqcnn_hip.so plans conv an
 GetInPdMat + CalcFeatMap_ConvAprx (src/CaffeEva.cc:1261-1296, :760-868) for a launch geometry is a pure function of plain
 numbers; these tests pin the decisions the measured profiles are made of and the properties the decision rules promise."""
 import ctypes as C
+import os
 
+import numpy as np
 import pytest
 
 from conftest import pkg
@@ -146,6 +148,79 @@ def test_malformed_geometry_is_refused(planner):
     o = (C.c_int * 8)(1, 1, 1, 1, 1, 1, 0, 64)
     assert lib.qcnn_plan_conv_query(g, o, None, None) != 0
 
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The recorded sweep: every conv geometry of the six models x panel counts x option sets through qcnn_plan_conv_query, against
+# tests/golden/planner_sweep.npz (recorded once, from the planner as it stood when this test was added; a rewrite of the planner's
+# pricing has to reproduce it.  `python tests/test_planner_cpu.py` rewrites the file from the library at hand: only for a change
+# that is MEANT to move a decision).
+# ----------------------------------------------------------------------------------------------------------------------
+SWEEP_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "planner_sweep.npz")
+SWEEP_PANELS = (1, 2, 3, 4, 5, 8, 16)
+# (split, slide, sym, sym8, half8, lut, flags, scratch Mi)
+SWEEP_OPTIONS = (
+    (1, 1, 1, 1, 1, 1, 0, 64),       # library defaults
+    (1, 1, 1, 1, 1, 1, 2, 64),       # concurrent sub-batches
+    (0, 1, 1, 1, 1, 1, 0, 64),       # no split
+    (1, 1, 1, 1, 0, 1, 0, 64),       # no half-panel family
+    (1, 1, 1, 0, 0, 1, 0, 64),       # no eight-wave family
+    (1, 0, 0, 0, 0, 1, 0, 64),       # everything off but the split
+    (1, 1, 1, 1, 1, 0, 0, 64),       # exact builder
+    (1, 2, 1, 1, 1, 1, 0, 64),       # forced: 16-wave sliding
+    (1, 1, 2, 0, 0, 1, 0, 64),       # 16-wave symmetric
+    (1, 1, 1, 2, 0, 1, 0, 64),       # eight-wave tile form
+    (1, 1, 1, 3, 0, 1, 0, 64),       # eight-wave sliding form
+    (1, 1, 1, 1, 2, 1, 0, 64),       # half-panel tile form
+    (1, 1, 1, 1, 3, 1, 0, 64),       # half-panel sliding form
+    (1, 1, 1, 1, 1, 1, 0, 0),        # no scratch
+    (1, 1, 1, 1, 1, 1, 0, 4),        # 4 Mi floats of scratch
+)
+
+
+def sweep_queries():
+    """(geom[14], opts[8]) of the sweep: the distinct conv layers of every model in topology.MODELS x SWEEP_PANELS x SWEEP_OPTIONS."""
+    geoms = []
+    for model in ("AlexNet", "CaffeNet", "VggCnnS", "VGG16", "CaffeNetFGB", "CaffeNetFGD"):
+        for geom in conv_geoms(model, 1).values():
+            if geom[:13] not in geoms:
+                geoms.append(geom[:13])
+    assert set(topo.MODELS) == {"AlexNet", "CaffeNet", "VggCnnS", "VGG16", "CaffeNetFGB", "CaffeNetFGD"}
+    return [(g + [panels], list(o)) for g in geoms for panels in SWEEP_PANELS for o in SWEEP_OPTIONS]
+
+
+def run_sweep(lib):
+    """{geom [n][14], opts [n][8], costs [n][7], choice [n][13]} of sweep_queries() through lib.qcnn_plan_conv_query."""
+    lib.qcnn_plan_conv_query.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    queries = sweep_queries()
+    costs, choice = np.zeros((len(queries), 7), np.float64), np.zeros((len(queries), 13), np.int32)
+    for i, (g, o) in enumerate(queries):
+        c, ch = (C.c_double * 7)(), (C.c_int * 13)()
+        assert lib.qcnn_plan_conv_query((C.c_int * 14)(*g), (C.c_int * 8)(*o), c, ch) == 0, (g, o)
+        costs[i], choice[i] = list(c), list(ch)
+    return dict(geom=np.array([g for g, _ in queries], np.int32), opts=np.array([o for _, o in queries], np.int32), costs=costs, choice=choice)
+
+
+def test_sweep_matches_recorded_plans():
+    """Same decisions, same numbers: family, split, Z and every segment boundary identical to the recorded plan, every cost within
+    1e-12 relative (zero stays zero).  The bound is derived: the one numeric freedom is the order in which a CU's running sum takes
+    an item's fixed part, (top + a) + f against top + (a + f) — one rounding (2^-52 of the sum) per item, and a CU receives fewer
+    than 10^3 items in any scheduled branch of this sweep (ny x nSeg x column groups x panels / 256), so 10^3 x 2^-51 = 4.4e-13."""
+    rec = np.load(SWEEP_FILE)
+    fam, Z = rec["choice"][:, 0], rec["choice"][:, 2]
+    # the recorded data itself: every family, both kinds of Z split, every cost slot
+    assert set(fam.tolist()) == {TILE, SLIDE16, SYM16, SYM8, SYM8_SLIDE, HALF8, HALF8_SLIDE}
+    assert ((fam == TILE) & (Z > 1)).any() and ((fam == SYM8) & (Z > 1)).any()
+    assert (rec["costs"] > 0).any(axis=0).all()
+    now = run_sweep(C.CDLL(build.build_planner_cpu()))
+    assert np.array_equal(now["geom"], rec["geom"]) and np.array_equal(now["opts"], rec["opts"])
+    bad = np.nonzero((now["choice"] != rec["choice"]).any(axis=1))[0]
+    assert bad.size == 0, [(rec["geom"][i].tolist(), rec["opts"][i].tolist(), rec["choice"][i].tolist(), now["choice"][i].tolist()) for i in bad[:4]]
+    zero = rec["costs"] == 0
+    assert (now["costs"][zero] == 0).all()
+    dev = np.abs(now["costs"] - rec["costs"])[~zero] / rec["costs"][~zero]
+    per_slot = [float((np.abs(now["costs"][:, k] - rec["costs"][:, k])[~zero[:, k]] / rec["costs"][:, k][~zero[:, k]]).max()) for k in range(7)]
+    print("largest relative cost deviation per slot:", dict(zip(COSTS, per_slot)))
+    assert dev.max() <= 1e-12, dict(zip(COSTS, per_slot))
 
 # ----------------------------------------------------------------------------------------------------------------------
 # FC layers: qk_choose_fc through qcnn_plan_fc_query.  The oracle below restates the rule as the engine's launch_layer spelt
@@ -327,3 +402,7 @@ def test_fc_malformed_geometry_is_refused(fc_planner):
     ch = (C.c_int * 2)()
     assert lib.qcnn_plan_fc_query((C.c_int * 8)(4096, 1000, 1024, 0, 4, 1, 8, 128), (C.c_int * 7)(1, 1, 1, 1, 0, 0, -1), ch) != 0   # K = 0
     assert lib.qcnn_plan_fc_query((C.c_int * 8)(4096, 1000, 1024, 32, 4, 1, 8, 129), (C.c_int * 7)(1, 1, 1, 1, 0, 0, -1), ch) != 0  # live > 128
+
+
+if __name__ == "__main__":      # the recorder: writes the fixture from the planner library as built from this tree
+    np.savez_compressed(SWEEP_FILE, **run_sweep(C.CDLL(build.build_planner_cpu())))
