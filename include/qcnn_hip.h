@@ -47,6 +47,7 @@
  *   / _read / _end              the layers' input maps where they lie: calibration sets of thousands of images
  *   qcnn_run_layer              CaffeEva::CalcFeatMap on one layer         src/CaffeEva.cc:625-670
  *   qcnn_get_layer_output       featMapLst[l] read-back (parity dumps)     include/CaffeEva.h:109
+ *   qcnn_map_diff               (no counterpart) featMapLst[l] of two models compared on the device: propagated response error
  *   qcnn_get_layer_ms           swIndvLayerLst / DispElpsTime              src/CaffeEva.cc:297-326
  *   qcnn_group_*                the image loop of ExecForwardPass(void)    src/CaffeEva.cc:151-211
  *                               spread over the GPUs of one node (the reference has one loop on one core)
@@ -67,6 +68,7 @@ extern "C" {
                               * qcnn_model_set_layer_shape accepts up to 256 code words per sub-space; qcnn_group_forward */
 
 #define QCNN_SMALL_BATCH_MAX 3   /* batches up to this size can take the few-image kernels (QCNN_OPT_SMALL_BATCH) */
+#define QCNN_DIFF_CHUNK_ROWS 64  /* qcnn_map_diff: 128-image rows of one channel that one workgroup folds into one partial row */
 
 typedef struct QcnnCtx QcnnCtx;
 
@@ -636,6 +638,36 @@ int qcnn_host_free(void* ptr);
 int qcnn_get_layer_output(QcnnCtx* ctx, int l, int n, float* host_out);
 /* Same for images [first, first + n) of the last forward (e.g. one image of the last, ragged panel). */
 int qcnn_get_layer_output_range(QcnnCtx* ctx, int l, int first, int n, float* host_out);
+/* Response error of one model against another, on the device: feature map l of the LAST forward of ctx (the subject, a) against
+ * the same map of the last forward of ref (the reference, b), images [0, n), read where both forwards left them (panels
+ * [E][128]) in one streaming pass — nothing but C rows of six doubles crosses PCIe.  (No counterpart in the reference, which
+ * ships finished parameters; the quantity is the propagated response error of Wu et al., CVPR'16, section 5.)
+ * Element e of an image has channel c = e % C (NHWC element order; behind an FC layer C is the node count and H * W = 1).  A
+ * pair (image i < n, element e) is COUNTED when both values are finite; otherwise it adds 1 to `nonfinite` of its channel and
+ * contributes to nothing else.  For a counted pair d = (double)a - (double)b — exact: the subtraction is never made in fp32.
+ * Per channel, in fp64:
+ *   count      counted pairs                     nonfinite  the others
+ *   sum_d      sum of d                          sum_d2     sum of d * d (the product rounded once, then added)
+ *   sum_ref2   sum of (double)b * (double)b      max_abs_d  largest |d| (0 when nothing is counted)
+ * total_host = the per-channel rows added in ascending channel order in fp64 (max for max_abs_d), from the very rows
+ * per_channel_host receives: total == fold(per_channel) bit for bit.
+ * ORDER OF SUMMATION: a function of (H, W, C, n) alone — no floating-point atomics.  The rows of a channel (one per panel and
+ * pixel, in that order) are cut into chunks of QCNN_DIFF_CHUNK_ROWS; a workgroup of 256 threads folds a chunk — thread t takes
+ * images 4 (t % 32) .. + 3 of rows t / 32, t / 32 + 8, ... in ascending order, the 256 threads are added by a halving tree —
+ * into one partial row of a scratch buffer; one wave per channel adds the partial rows (lane j: chunks j, j + 64, ... ascending,
+ * then a halving tree).  Two calls on the same maps return the same bits whatever QCNN_OPT_STREAMS, QCNN_OPT_SMALL_BATCH or
+ * the history of the contexts.  Lanes of images >= n contribute nothing, whatever an earlier, larger forward left there; nothing
+ * beyond ceil(n / 128) panels of either map is addressed.
+ * The two models need not be the same: only fm[l] must have the same (H, W, C).  ctx == ref is allowed (zeros, sum_ref2 =
+ * sum of a * a).  Blocking: waits for both contexts' streams, runs on ctx's stream, copies the rows to the host.  The scratch
+ * belongs to ctx (first use, grown on demand, freed with the context; no part of the commit plan).
+ * Checked before any launch — non-zero, the cause in qcnn_last_error(ctx), both contexts still usable: a NULL context or
+ * total_host; contexts on different devices; l outside [0, layer_cnt] of either; fm[l] dims that differ; n <= 0 or above either
+ * context's last batch; a map either context cannot read back (the conditions and messages of qcnn_get_layer_output: no forward
+ * yet, not materialised, fused away under QCNN_OPT_KEEP_ALL = 0).  With ctx == NULL the message is qcnn_last_error(NULL)'s. */
+typedef struct { double count, nonfinite, sum_d, sum_d2, sum_ref2, max_abs_d; } QcnnMapDiff;
+int qcnn_map_diff(QcnnCtx* ctx, QcnnCtx* ref, int l, int n,
+                  QcnnMapDiff* total_host, QcnnMapDiff* per_channel_host /* [C of fm[l]] or NULL */);
 /* Run layer `layer` alone on n images: in_host is fm[layer] NHWC per image (FC layers: the flat
  * vector in the order the reference consumes it), out_host receives fm[layer+1] (blocking). */
 int qcnn_run_layer(QcnnCtx* ctx, int layer, const float* in_host, int n, float* out_host);

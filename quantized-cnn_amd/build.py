@@ -26,7 +26,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 HIP_SOURCES = ["qcnn_kernels.hip", "qcnn_sym8.hip", "qcnn_half8.hip", "qcnn_planner.hip", "qcnn_glue.hip", "qcnn_small.hip", "qcnn_dense.hip", "qcnn_decoded.hip", "qcnn_quantize.hip", "qcnn_ec.hip", "qcnn_engine.hip", "qcnn_engine_params.hip", "qcnn_engine_run.hip", "qcnn_engine_quant.hip", "qcnn_engine_u8.hip",
-               "qcnn_engine_host.hip", "qcnn_group.hip", "qcnn_glue_yuv.hip"]
+               "qcnn_engine_host.hip", "qcnn_group.hip", "qcnn_glue_yuv.hip", "qcnn_diff.hip"]
 HIP_FLAGS = ["-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-ffp-contract=off", "-Wall",
              "-Wno-unused-function"]
 

@@ -16,6 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG), "include", "qcnn_hip.h")
 OPT_LUT_MODE, OPT_KEEP_ALL, OPT_PROFILE, OPT_STREAMS, OPT_SMALL_BATCH, OPT_SPLIT, OPT_HOST_CHUNK, OPT_SLIDE, OPT_DECODE, OPT_SYM, OPT_SYM8, OPT_PACKED_FC, OPT_DIRECT_DEC, OPT_HALF8, OPT_DEC_BF16SPLIT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14
 LUT_EXACT, LUT_MFMA, LUT_MFMA_F16, LUT_MFMA_F16ACC = 0, 1, 2, 3
 SMALL_BATCH_MAX = 3        # QCNN_SMALL_BATCH_MAX (include/qcnn_hip.h)
+DIFF_CHUNK_ROWS = 64       # QCNN_DIFF_CHUNK_ROWS (include/qcnn_hip.h): rows of one channel a workgroup of qcnn_map_diff folds
 
 
 class QcnnLayerDesc(C.Structure):
@@ -53,6 +54,15 @@ class QcnnSrcYuv(C.Structure):
     _fields_ = [("y_offset", C.c_uint64), ("cb_offset", C.c_uint64), ("cr_offset", C.c_uint64), ("y_row_stride", C.c_int64),
                 ("c_row_stride", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("y_pix_stride", C.c_int32),
                 ("c_pix_stride", C.c_int32), ("sub_y", C.c_int32), ("sub_x", C.c_int32), ("matrix", C.c_int32)]
+
+
+class QcnnMapDiff(C.Structure):
+    """One row of qcnn_map_diff (a channel, or the total): six doubles, 48 bytes."""
+    _fields_ = [("count", C.c_double), ("nonfinite", C.c_double), ("sum_d", C.c_double), ("sum_d2", C.c_double),
+                ("sum_ref2", C.c_double), ("max_abs_d", C.c_double)]
+
+
+MAP_DIFF_FIELDS = tuple(f for f, _ in QcnnMapDiff._fields_)
 
 
 class QcnnAnchorView(C.Structure):
@@ -158,6 +168,7 @@ def load():
     lib.qcnn_host_free.argtypes = [vp]
     lib.qcnn_get_layer_output.argtypes = [vp, i, i, f32p]
     lib.qcnn_get_layer_output_range.argtypes = [vp, i, i, i, f32p]
+    lib.qcnn_map_diff.argtypes = [vp, vp, i, i, C.POINTER(QcnnMapDiff), vp]
     lib.qcnn_run_layer.argtypes = [vp, i, f32p, i, f32p]
     lib.qcnn_get_layer_split.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
     lib.qcnn_get_layer_dec_form.argtypes = [vp, i, C.POINTER(i), C.POINTER(C.c_longlong)]

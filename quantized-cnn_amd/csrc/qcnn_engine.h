@@ -142,6 +142,8 @@ struct QcnnCtx {
   size_t fcMaxCt = 0;
   float* viewMean = nullptr;         // qcnn_forward_u8_views: panels [classes][128] of the probabilities averaged over an image's views —
   size_t viewMeanElems = 0;          // allocated at its first call, grown when one needs more, freed with the context (no part of the plan)
+  double* diffScratch = nullptr;     // qcnn_map_diff: per-channel rows + partial rows of its two passes, owned like viewMean
+  size_t diffScratchDoubles = 0;
   // qcnn_forward_u8_resized_views: the source-image descriptors of a call travel host -> pinned -> device through one of two
   // staging sets the context owns (first use, grown on demand, freed with the context).  ev is recorded behind the pack kernel
   // that reads the set: the next call that takes the set waits for it before it rewrites (or frees) the buffers.
@@ -244,6 +246,7 @@ int ensure_u8_stream(QcnnCtx* c, size_t srcBytes);       // ... + what the 8-bit
 float* ensure_conv_partial(QcnnCtx* c);                  // convPartial; nullptr: the device has no room for it (no error)
 uint32_t* ensure_dec_guard(QcnnCtx* c, int sub);         // decGuard's region of sub-batch `sub`; nullptr after fail()
 int views_scratch(QcnnCtx* c, int n, bool wantMean);     // viewMean for n images
+int diff_scratch(QcnnCtx* c, size_t doubles);            // diffScratch of at least that many doubles
 QcnnCtx::SrcStage* stage_take(QcnnCtx* c, size_t n, size_t each);   // the next descriptor staging set; nullptr after fail()
 
 // ---- qcnn_engine_params.hip: kTables, the one place that knows, per TableKind, when a layer has the table, how big it is and

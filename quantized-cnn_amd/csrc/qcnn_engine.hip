@@ -276,6 +276,18 @@ int views_scratch(QcnnCtx* c, int n, bool wantMean) {
   return 0;
 }
 
+// qcnn_map_diff, BEFORE its launches: the scratch of its two passes holds `doubles` doubles.
+int diff_scratch(QcnnCtx* c, size_t doubles) {
+  if (c->diffScratchDoubles < doubles) {             // grow: the call is blocking, nothing on the stream still reads the old one
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->diffScratch) (void)hipFree(c->diffScratch);
+    c->diffScratch = nullptr; c->diffScratchDoubles = 0;
+    HIP_TRY(c, hipMalloc(&c->diffScratch, doubles * sizeof(double)));
+    c->diffScratchDoubles = doubles;
+  }
+  return 0;
+}
+
 // The next of the two descriptor staging sets, large enough for n descriptors of `each` bytes (at least 64 of them); nullptr
 // after fail().  The last reader of the set taken — the pack kernel of the call before the previous one — must have passed
 // before its buffers are rewritten or freed.
@@ -357,6 +369,7 @@ int qcnn_ctx_destroy(QcnnCtx* c) {
   (void)hipStreamSynchronize(c->stream);
   free_model(c);
   if (c->viewMean) (void)hipFree(c->viewMean);
+  if (c->diffScratch) (void)hipFree(c->diffScratch);
   for (int k = 0; k < 2; ++k) {
     if (c->u8s.src[k]) (void)hipFree(c->u8s.src[k]);
     if (c->u8s.evCounted[k]) (void)hipEventDestroy(c->u8s.evCounted[k]);

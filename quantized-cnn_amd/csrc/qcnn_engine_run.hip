@@ -542,6 +542,49 @@ int qcnn_get_layer_output_range(QcnnCtx* c, int l, int first, int n, float* host
   return 0;
 }
 
+// Map l of c's last forward against the same map of ref's (include/qcnn_hip.h): every check first, then two launches on c's
+// stream and C rows of six doubles to the host; the total is folded here from the rows the caller receives.
+int qcnn_map_diff(QcnnCtx* c, QcnnCtx* ref, int l, int n, QcnnMapDiff* total_host, QcnnMapDiff* per_channel_host) {
+  if (!c) return fail(nullptr, "qcnn_map_diff: ctx == NULL");
+  if (!ref) return fail(c, "qcnn_map_diff: ref == NULL");
+  if (!total_host) return fail(c, "qcnn_map_diff: total_host == NULL");
+  if (c->device != ref->device)
+    return fail(c, "qcnn_map_diff: the contexts are on different devices (%d and %d)", c->device, ref->device);
+  if (l < 0 || l > c->L) return fail(c, "feature map %d out of range", l);
+  if (l > ref->L) return fail(c, "feature map %d out of range of the reference context (%d layers)", l, ref->L);
+  if ((int)c->dims.size() != c->L + 1 || (int)ref->dims.size() != ref->L + 1) return fail(c, "feature map %d is not available", l);
+  const FmDims da = c->dims[l], db = ref->dims[l];
+  if (da.h != db.h || da.w != db.w || da.c != db.c)
+    return fail(c, "feature map %d has different dims in the two contexts: %d x %d x %d against %d x %d x %d", l, da.h, da.w, da.c,
+                db.h, db.w, db.c);
+  if (layer_output_ok(c, l)) return 1;
+  if (ref != c && layer_output_ok(ref, l)) return fail(c, "reference context: %s", std::string(ref->err).c_str());
+  if (n <= 0) return fail(c, "n = %d: at least one image", n);
+  if (n > c->lastN) return fail(c, "n = %d exceeds the last forward's batch %d", n, c->lastN);
+  if (n > ref->lastN) return fail(c, "n = %d exceeds the reference context's last forward's batch %d", n, ref->lastN);
+  const int HW = da.h * da.w, C = da.c;
+  const size_t doubles = qk_map_diff_doubles(HW, C, n);
+  if (!doubles) return fail(c, "qcnn_map_diff: feature map %d (%d x %d x %d, %d images) is beyond one launch", l, da.h, da.w, C, n);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (diff_scratch(c, doubles)) return 1;
+  if (ref != c) HIP_TRY(c, hipStreamSynchronize(ref->stream));     // run_layers joined the auxiliary streams into it
+  hipError_t e = qk_map_diff(c->lastFm[l], ref->lastFm[l], HW, C, n, c->diffScratch, c->stream);
+  if (e != hipSuccess) return fail(c, "map diff launch failed: %s", hipGetErrorString(e));
+  std::vector<QcnnMapDiff> own;
+  QcnnMapDiff* rows = per_channel_host;
+  if (!rows) { own.resize(C); rows = own.data(); }
+  HIP_TRY(c, hipMemcpyAsync(rows, c->diffScratch, (size_t)C * sizeof(QcnnMapDiff), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  QcnnMapDiff t = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int ch = 0; ch < C; ++ch) {                   // ascending channel order, fp64
+    t.count += rows[ch].count; t.nonfinite += rows[ch].nonfinite;
+    t.sum_d += rows[ch].sum_d; t.sum_d2 += rows[ch].sum_d2; t.sum_ref2 += rows[ch].sum_ref2;
+    if (rows[ch].max_abs_d > t.max_abs_d) t.max_abs_d = rows[ch].max_abs_d;
+  }
+  *total_host = t;
+  return 0;
+}
+
 int qcnn_run_layer(QcnnCtx* c, int layer, const float* in_host, int n, float* out_host) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->committed) return fail(c, "model not committed");

@@ -525,6 +525,13 @@ hipError_t qk_pack_rows(const float* in, float* dst, int n, int E, hipStream_t s
 // panels [E][128] -> [n][E]
 hipError_t qk_unpack_rows(const float* src, float* out, int n, int E, hipStream_t st);
 
+// Two maps of panels [HW * C][128] compared over images [0, n) (qcnn_diff.hip, behind qcnn_map_diff; the contract is
+// include/qcnn_hip.h's).  scratch: qk_map_diff_doubles(HW, C, n) doubles; its first C * 6 hold the per-channel rows
+// (count, nonfinite, sum_d, sum_d2, sum_ref2, max_abs_d) when the stream has passed, the partial rows lie behind them.
+// a == b is allowed.  0 doubles / hipErrorInvalidValue: a shape whose grid would not fit 31 bits.
+size_t qk_map_diff_doubles(int HW, int C, int n);
+hipError_t qk_map_diff(const float* a, const float* b, int HW, int C, int n, double* scratch, hipStream_t st);
+
 // Product-quantisation k-means of one dense layer (qcnn_quantize.hip, behind qcnn_quantize_layer).  pts [M][N][Cs] (dims >= CsEff
 // zero), ctrd [M][K][Cs], asmt / dmin [M][N]; chg / active [M] (active == NULL: every sub-space); first = 1: no changed-flags.
 #define QCNN_PQ_MAX_K 256

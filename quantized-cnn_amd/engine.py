@@ -613,6 +613,25 @@ class QcnnEngine:
         self._chk(self.lib.qcnn_get_layer_output_range(self.h, l, first, n, out.ctypes.data))
         return out
 
+    def map_diff(self, ref, l: int, n: int, per_channel: bool = False):
+        """Feature map l of this engine's last forward against the same map of ``ref``'s, images [0, n), compared on the device
+        (qcnn_map_diff; blocking).  With d = (double)a - (double)b over the pairs whose two values are finite, returns
+        dict(count, nonfinite, sum_d, sum_d2, sum_ref2, max_abs_d, rel_err = sqrt(sum_d2 / sum_ref2), mean_d = sum_d / count);
+        per_channel=True adds ``channels``: float64 [C][6], the same six sums per channel, whose fold is the total to the bit.
+        ``ref`` may hold another model: only the map's dims must agree.  Both engines need OPT_KEEP_ALL = 1 for maps the fast
+        path fuses away."""
+        tot = capi.QcnnMapDiff()
+        rows = None
+        if per_channel:
+            rows = np.empty((self.fm_dims(l)[2], len(capi.MAP_DIFF_FIELDS)), np.float64)
+        rc = self.lib.qcnn_map_diff(self.h, getattr(ref, "h", None), int(l), int(n), C.byref(tot),
+                                    rows.ctypes.data if rows is not None else None)
+        self._chk(rc)
+        out = map_diff_summary({f: float(getattr(tot, f)) for f in capi.MAP_DIFF_FIELDS})
+        if per_channel:
+            out["channels"] = rows
+        return out
+
     def run_layer(self, l: int, x, n: int):
         x = np.ascontiguousarray(x, np.float32)
         h, w, c = self.fm_dims(l + 1)
@@ -658,6 +677,16 @@ class QcnnEngine:
 
     def reset_layer_ms(self):
         self._chk(self.lib.qcnn_reset_layer_ms(self.h))
+
+
+def map_diff_summary(sums):
+    """The six sums of a map_diff row (a dict keyed by capi.MAP_DIFF_FIELDS) plus what is derived from them: rel_err =
+    sqrt(sum_d2 / sum_ref2) (0.0 when both are 0, inf when only sum_ref2 is) and mean_d = sum_d / count (0.0 without pairs)."""
+    out = {f: float(sums[f]) for f in capi.MAP_DIFF_FIELDS}
+    d2, r2 = out["sum_d2"], out["sum_ref2"]
+    out["rel_err"] = float(np.sqrt(d2 / r2)) if r2 > 0.0 else (0.0 if d2 == 0.0 else float("inf"))
+    out["mean_d"] = out["sum_d"] / out["count"] if out["count"] > 0.0 else 0.0
+    return out
 
 
 def _host_batches(fn, obj, batches, out_hwc, want_prob, want_top5):

@@ -156,6 +156,68 @@ def quantize_model(eng, in_chw, layers, dense, spec=None, max_iter=DEFAULT_MAX_I
     return params, stats
 
 
+def _forward_float(eng, batch):
+    x = np.ascontiguousarray(batch, np.float32)
+    return len(x), eng.forward_host(x, want_prob=False)[1]
+
+
+def default_report_maps(layers):
+    """The maps response_report compares unless told otherwise: the output map i + 1 of every conv / FC layer i, and the last."""
+    maps = [i + 1 for i, ly in enumerate(layers) if ly["type"] in (CONV, FCNT)]
+    return maps if len(layers) in maps else maps + [len(layers)]
+
+
+def response_report(eng, ref, batches, maps=None, forward=None, per_channel=False):
+    """How far every feature map of the model in ``eng`` (the subject, e.g. a quantised network) is from the same map of the
+    model in ``ref`` (e.g. the dense network) on the same inputs, the error of the layers in front carried along, and how often
+    the two agree on the answer — compared on the device where the forwards left the maps (QcnnEngine.map_diff).  For every
+    batch: ``forward(ref, batch)`` then ``forward(eng, batch)``, each returning (n, top5 [n][5]) — default: forward_host on a
+    float [n][C][H][W] array; pass a callable for 8-bit or YCbCr sources, one batch per call (only the last batch's maps
+    survive a *_host_batches call) — then ``eng.map_diff(ref, l, n)`` for every l of ``maps`` (default_report_maps), added
+    over the batches on the host in fp64 (sums add, max_abs_d takes the maximum).  Returns (report {l: dict with map_diff's
+    keys, derived from the accumulated sums; with per_channel=True also ``channels`` [C][6], accumulated the same way, and the
+    totals are then the fold of those rows in ascending channel order, to the bit}, agree dict(n, top1_equal = images whose
+    first predictions are equal, ref_top1_in_top5 = images whose reference first prediction is among the subject's five)).
+    Both engines need OPT_KEEP_ALL = 1 for maps the fast path fuses away: such a map raises QcnnError, it is never skipped."""
+    from .engine import map_diff_summary
+    forward = forward or _forward_float
+    maps = [int(l) for l in (default_report_maps(eng.layers) if maps is None else maps)]
+    fields = capi.MAP_DIFF_FIELDS
+    imax = fields.index("max_abs_d")
+    sums = {l: dict.fromkeys(fields, 0.0) for l in maps}
+    chans = {}
+    agree = dict(n=0, top1_equal=0, ref_top1_in_top5=0)
+    for batch in batches:
+        n_ref, t_ref = forward(ref, batch)
+        n, t_eng = forward(eng, batch)
+        if n != n_ref:
+            raise ValueError("response_report: the two forwards ran %d and %d images" % (n_ref, n))
+        t_ref, t_eng = np.asarray(t_ref).reshape(n, -1), np.asarray(t_eng).reshape(n, -1)
+        agree["n"] += int(n)
+        agree["top1_equal"] += int(np.count_nonzero(t_eng[:, 0] == t_ref[:, 0]))
+        agree["ref_top1_in_top5"] += int(np.count_nonzero((t_eng == t_ref[:, :1]).any(axis=1)))
+        for l in maps:
+            r = eng.map_diff(ref, l, n, per_channel=per_channel)
+            s = sums[l]
+            for f in fields:
+                s[f] = max(s[f], float(r[f])) if f == "max_abs_d" else s[f] + float(r[f])
+            if per_channel:
+                ch = np.asarray(r["channels"], np.float64)
+                if l not in chans:
+                    chans[l] = ch.copy()
+                else:
+                    mx = np.maximum(chans[l][:, imax], ch[:, imax])
+                    chans[l] += ch
+                    chans[l][:, imax] = mx
+    for l, ch in chans.items():                        # per_channel: the totals are the fold of the rows handed back, to the bit
+        for j, f in enumerate(fields):
+            sums[l][f] = float(ch[:, j].max()) if j == imax else float(np.add.accumulate(ch[:, j])[-1])
+    report = {l: map_diff_summary(sums[l]) for l in maps}
+    for l, ch in chans.items():
+        report[l]["channels"] = ch
+    return report, agree
+
+
 def _model_tables(model):
     if isinstance(model, str):
         in_chw, layers, _, _ = topology.MODELS[model]
