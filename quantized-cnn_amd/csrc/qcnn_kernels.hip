@@ -516,10 +516,15 @@ __device__ __forceinline__ void mfma_store(MfmaOps<KT, KS>& o, int Cs, int D, in
                                            bool maskA = true) {
   if (maskA) {
     mfma_mask<KT, KS>(o, Cs, D, m0, mEnd, lane, true, true);
-  } else {                        // kept operands: one sub-space, always the same -> the activation mask is lane-constant
-    const bool ok = (lane >> 4) < min(D, Cs);
+  } else if constexpr (MfmaOps<KT, KS>::SUBS == 1) {   // kept operands, K = 128: one sub-space, always the same -> the activation
+    const bool ok = (lane >> 4) < min(D, Cs);          // mask is lane-constant
 #pragma unroll
     for (int it = 0; it < 2; ++it) o.b[it][0][0] = ok ? o.b[it][0][0] : 0.0f;
+  } else {
+    // kept operands, K <= 64: the ONE stage of a pixel holds up to 128 / K sub-spaces.  The code book was masked once; the
+    // activations are masked here in EVERY sub-space slot — a slot past M, or the dims a ragged last sub-space lacks, hold the
+    // next group's / pixel's / panel's activations, which a zero code-book operand does not silence when they are NaN or Inf
+    mfma_mask<KT, KS>(o, Cs, D, m0, mEnd, lane, false, true);
   }
   if constexpr (KS == 1) {
     if (f16) mfma_multiply<KT, KS, BUF, 1>(o, bw, f16); else mfma_multiply<KT, KS, BUF, 0>(o, bw, f16);

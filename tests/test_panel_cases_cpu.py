@@ -32,8 +32,8 @@ RING = LUT_STAGE_BUFFERS * PROGRAM_ROW_BUFFERS      # a tile with more stages th
 
 
 def plan(planner, name, panels, opts):
-    """(costs by family, choice) of shape `name` at `panels` panels under the option dictionary of a family descriptor."""
-    kind, g, M, K, Cs, _ = tp.SHAPES[name]
+    """(costs by family, choice) of shape `name` (or a shape tuple) at `panels` panels under the option dictionary of a family descriptor."""
+    kind, g, M, K, Cs, _ = tp.SHAPES[name] if isinstance(name, str) else name
     Ho, Wo = tp.out_hw(g)
     geom = [g["H"], g["W"], g["Cin"], Ho, Wo, g["Ct"], g["knl"], g["stride"], g["pad"], g["grp"], M, Cs, K, panels]
     return planner(geom, **{k: opts[k] for k in ("split", "slide", "sym", "sym8", "half8", "lut")})
@@ -173,8 +173,9 @@ def derive(name):
     """What the launchers choose for a pn_* shape, family by family, in the layout of table_probe.PANEL_REACH:
        tile / sym16 / sym8 / half8:   (cpw, th, tw[, wave sets], channel chunks per group, (tilesY, tilesX), stages of the heaviest tile)
        slide16 / sym8_slide / half8_slide: (cpw, slots, columns per strip[, wave sets], chunks, strips, stages of a whole-column strip)
-    and G, the sub-spaces of a pixel's last stage, the stages per source pixel (pseudo sub-spaces counted)."""
-    kind, g, M, K, Cs, _ = tp.SHAPES[name]
+    and G, the sub-spaces of a pixel's last stage, the stages per source pixel (pseudo sub-spaces counted).  `name`: a key of
+    table_probe.SHAPES or a shape tuple."""
+    kind, g, M, K, Cs, _ = tp.SHAPES[name] if isinstance(name, str) else name
     Cg, Ctg = g["Cin"] // g["grp"], g["Ct"] // g["grp"]
     P = pseudo(K)
     Mk, Kk = M * P, (128 if P > 1 else K)               # as the kernels see the layer
