@@ -200,6 +200,8 @@ int qcnn_ctx_device(const QcnnCtx* ctx);          /* HIP device ordinal of the c
 void* qcnn_ctx_stream(const QcnnCtx* ctx);        /* the hipStream_t the context enqueues on */
 
 /* ---- model ---- */
+/* qcnn_model_begin refuses (non-zero, qcnn_last_error names the layer and the rule) a conv layer whose padSiz is negative or >= knlSiz:
+ * every window must hold a pixel of the map.  The context stays usable: a later qcnn_model_begin starts over. */
 int qcnn_model_begin(QcnnCtx* ctx, int layer_cnt, const QcnnLayerDesc* layers, int in_c, int in_h, int in_w);
 /* Declare the quantisation shape of conv/FC layer `layer` (M sub-spaces, K codewords, Cs dims each).
  * Must precede qcnn_model_commit for every conv/FC layer.  K <= 256 — everything the reference's uint8 assignments can
@@ -702,7 +704,7 @@ int qcnn_get_layer_segments(QcnnCtx* ctx, int layer, int* seg_beg9, int* n_seg);
  *   QCNN_OPT_STREAMS > 1), partial-sum scratch in Mi floats.
  *   costs[7] (predicted stage-times; 0 = not eligible) = tile kernel, 16-wave sliding, 16-wave symmetric, eight-wave tile, eight-wave
  *   sliding, half-panel tile, half-panel sliding.     choice[13] = family code (what qcnn_get_layer_split reports: -1 tile, -2, -4, -5,
- *   -6, -9, -10; never -11: the few-image kernels are the engine's choice, not the planner's), first split tile, slices, segments per column, nine segment boundaries.  Returns non-zero on a malformed geometry. */
+ *   -6, -9, -10; never -11: the few-image kernels are the engine's choice, not the planner's), first split tile, slices, segments per column, nine segment boundaries.  Returns non-zero on a malformed geometry, pad < 0 and pad >= knl included (as qcnn_model_begin). */
 int qcnn_plan_conv_query(const int* geom, const int* opts, double* costs, int* choice);
 
 /* ---- timing (QCNN_OPT_PROFILE = 1) ---- */

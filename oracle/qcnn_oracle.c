@@ -292,7 +292,11 @@ void qo_conv_prec(const float* src, int B, int H, int W, int Cin, int knl, int s
                * Reproduced as is: the reference's behaviour is the specification of this path. */
               const int hoL = imax(0, (pad - kh - 1) / stride + 1), hoU = imin(Ho - 1, (pad - kh + H - 1) / stride);
               const int woL = imax(0, (pad - kw - 1) / stride + 1), woU = imin(Wo - 1, (pad - kw + W - 1) / stride);
-              const float x = (ho >= hoL && ho <= hoU && wo >= woL && wo <= woU)
+              /* The UPPER bounds truncate towards zero as well: for -stride < pad - kh + H - 1 < 0 (a map shorter than the
+               * kernel's reach, e.g. H = 1, 3x3 / 2, pad 1, kh = 2) hoU is 0 instead of -1 and hi = H, one row behind the
+               * map — the reference reads outside its input there, which is no value to reproduce.  The one place this path
+               * leaves the reference: a tap with hi >= H or wi >= W contributes 0, like every other tap outside the map. */
+              const float x = (ho >= hoL && ho <= hoU && wo >= woL && wo <= woU && hi < H && wi < W)
                                   ? src[(((size_t)b * H + hi) * W + wi) * Cin + g * Cg + ci] : 0.0f;
               const float va = wr[k] * 1.0f;                    /* pa[ik] * alpha */
               acc = acc + va * x;

@@ -12,6 +12,12 @@
 // equal to the reference within the north-star tolerance (1e-4), like every MFMA path of this library.
 // The reference's im2col drops some taps at output row / column 0 of strided layers (truncating division on a negative
 // numerator, :1219,1223); that is reproduced: the reference's behaviour is the specification.
+// ONE exception: the UPPER tap bound (pad - kh + H - 1) / stride truncates towards zero too, so for
+// -stride < pad - kh + H - 1 < 0 (a map shorter than the kernel reaches below it, e.g. H = 1, 3x3 / 2, pad 1, kh = 2) it
+// comes out as 0 instead of -1 and output row / column 0 takes a tap whose source row / column is H / W: one past the map.
+// The compiled reference reads outside its input there (no value to reproduce); here the row behind the map is the next
+// panel row — another image's activations.  Such a tap contributes 0 (hi < H, wi < W), as every other tap outside the map;
+// wherever pad - kh + H - 1 >= 0 the guard changes nothing (tests/test_tiny_cases_cpu.py sweeps it).
 #include "qcnn_kernels.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -40,11 +46,11 @@ __global__ __launch_bounds__(256) void k_dense(DenseParams p) {
     const int hi = ho * p.stride - p.pad + kh;
     // rows this tap fills in the reference's im2col buffer (src/CaffeEva.cc:1219-1222, C integer division as written)
     const int hoL = max(0, (p.pad - kh - 1) / p.stride + 1), hoU = min(p.Ho - 1, (p.pad - kh + p.H - 1) / p.stride);
-    if (ho < hoL || ho > hoU) continue;
+    if (ho < hoL || ho > hoU || hi >= p.H) continue;    // hi >= H: see the header — the one place this path leaves the reference
     for (int kw = 0; kw < p.knl; ++kw) {
       const int wi = wo * p.stride - p.pad + kw;
       const int woL = max(0, (p.pad - kw - 1) / p.stride + 1), woU = min(p.Wo - 1, (p.pad - kw + p.W - 1) / p.stride);
-      if (wo < woL || wo > woU) continue;
+      if (wo < woL || wo > woU || wi >= p.W) continue;
       const float* __restrict__ xr = src + ((size_t)(hi * p.W + wi) * p.Cin + grp * Cg) * PANEL;
       const float* __restrict__ wr = p.wt + ((size_t)(grp * p.knl * p.knl + kh * p.knl + kw) * Cg) * Ctg + c0;
       for (int ci = 0; ci < Cg; ci += 4) {

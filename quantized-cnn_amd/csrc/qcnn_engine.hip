@@ -446,6 +446,11 @@ int qcnn_model_begin(QcnnCtx* c, int layer_cnt, const QcnnLayerDesc* layers, int
       case QCNN_CONV:
         if (d.grpCnt <= 0 || d.stride <= 0 || d.knlSiz <= 0 || ch % d.grpCnt || d.knlCnt % d.grpCnt)
           return fail(c, "layer %d: bad conv geometry", l);
+        // a window must touch the map: with padSiz >= knlSiz a tile of the table kernels can lie wholly in the padding (no source
+        // row or column at all), which their stage arithmetic does not provide for
+        if (d.padSiz < 0 || d.padSiz >= d.knlSiz)
+          return fail(c, "layer %d: conv padding %d is outside [0, kernel size %d): every window must hold a pixel of the map", l,
+                      d.padSiz, d.knlSiz);
         h = conv_out(h, d.knlSiz, d.stride, d.padSiz); w = conv_out(w, d.knlSiz, d.stride, d.padSiz); ch = d.knlCnt;
         break;
       case QCNN_POOL:

@@ -811,6 +811,7 @@ extern "C" int qcnn_plan_conv_query(const int* geom, const int* opts, double* co
   p.knl = geom[6]; p.stride = geom[7]; p.pad = geom[8]; p.grp = geom[9]; p.M = geom[10]; p.Cs = geom[11]; p.K = geom[12]; p.panels = geom[13];
   p.pd = 1; p.splitZ = 1;
   if (p.grp < 1 || p.Ct % p.grp || p.Cin % p.grp || p.panels < 1 || p.knl < 1 || p.stride < 1) return 1;
+  if (p.pad < 0 || p.pad >= p.knl) return 1;   // as qcnn_model_begin: a tile wholly in the padding has no stage
   QkPlanOptions o = {};
   o.split = opts[0]; o.slide = opts[1]; o.sym = opts[2]; o.sym8 = opts[3]; o.half8 = opts[4]; o.lutMode = opts[5]; o.inNchw = opts[6] & 1; o.concurrent = (opts[6] >> 1) & 1;
   o.scratchFloats = (size_t)opts[7] << 20;

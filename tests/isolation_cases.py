@@ -58,6 +58,10 @@ SHAPES = {
     "fr_small": ("fc", tp.fc_geom(918, 200), 230, 128, 4, None),      # fc_k128: few-image chunks 224 + 6
 }
 IG = sorted(n for n in SHAPES if n.startswith("ig_"))
+# the base rows of table_probe.TINY_SHAPES — maps of a few pixels, where nearly every tap of nearly every window is a clipping select
+# (a padding tap, a row or column of a tile larger than the map, a source pixel no window holds): the place a missing select hides.
+# Complete sub-spaces (4 x 8 dims for 32 channels): no operand over-read.  Their family reach is table_probe.TINY_REACH
+TG = sorted(tp.TINY_BASE)
 FR = sorted(n for n in SHAPES if n.startswith("fr_"))
 FR_FROM = {"fr_k128": "fa_k128", "fr_k64": "fa_k64", "fr_k32": "fx_slices", "fr_small": "fc_k128"}
 
@@ -66,6 +70,8 @@ def shape_of(name):
     """(kind, geometry, M, K, Cs) of a case: a new shape, a shape of table_probe.SHAPES or an FC case of exact_cases.FC."""
     if name in SHAPES:
         return SHAPES[name][:5]
+    if name in tp.TINY_SHAPES:
+        return tp.TINY_SHAPES[name][:5]
     if name in ec.FC:
         return ("fc",) + ec.FC[name][:4]
     return tp.SHAPES[name][:5]
@@ -190,6 +196,8 @@ def plan(kind, g, M, Cs, n=BATCH):
         H, W, Cin = g["H"], g["W"], g["Cin"]
         elems = [(0, 0, 0), (H - 1, W - 1, Cin - 1)]
         elems += [(h, w, chs[i % len(chs)]) for i, (h, w) in enumerate(pixels(g, len(free) - 2))]
+        # a map with fewer pixels than listed channels (the tg_* shapes): the channels the cycle did not reach, at the last pixel
+        elems += [(H - 1, W - 1, c) for c in chs if c not in {e[2] for e in elems}]
     assert len(elems) <= len(free)
     # spread over the free images: the poisons then sit in both halves of the full panel, not in its first lanes alone
     step = len(free) / len(elems)
@@ -252,6 +260,15 @@ POSITIONS = {
     "pn_k32_m18": (4, 9, 70), "pn_k10_m32": (4, 9, 70), "pn_k64_m9": (4, 9, 63), "pn_partial": (4, 9, 63), "pn_k200": (4, 9, 70),
     "pn_k256": (4, 9, 70), "pn_grp2_5x5": (9, 25, 77), "pn_s2_5x5": (4, 9, 35),
     "ig_grp2_ragged": (4, 9, 63), "ig_grp2_cs4_k32": (4, 9, 63), "ig_grp2_cs4_m5": (4, 9, 63),
+    "tg_1x1": (1, 1, 1), "tg_1x2": (2, 2, 2), "tg_col": (2, 3, 7), "tg_fit": (1, 1, 1), "tg_gap": (1, 1, 6), "tg_k5": (6, 6, 6),
+    "tg_pad2": (9, 9, 16), "tg_row": (2, 3, 4), "tg_s2": (4, 4, 4), "tg_s4": (1, 1, 3),
+}
+# On the tg_* maps "some, not all" cannot hold pixel by pixel: a 1 x 1 map has one output, a 5x5 window holds a whole 2 x 3 map, a
+# stride above the kernel size leaves source pixels no window holds.  Stated instead, per shape: (pixels whose poison reaches NO
+# output, pixels whose poison reaches EVERY output, pixels of the map); every other pixel reaches some and not all
+TG_PIXELS = {
+    "tg_1x1": (0, 1, 1), "tg_1x2": (0, 2, 2), "tg_col": (0, 0, 7), "tg_fit": (0, 9, 9), "tg_gap": (32, 0, 56), "tg_k5": (0, 6, 6),
+    "tg_pad2": (0, 0, 4), "tg_row": (0, 0, 4), "tg_s2": (0, 9, 12), "tg_s4": (22, 0, 36),
 }
 
 

@@ -567,6 +567,185 @@ PANEL_REACH = {
 PANEL_BATCH, PANEL_HALF_BATCHES, PANEL_SPLIT_BATCH = 131, (70, 5), 125     # a full panel + a ragged one of three; half panels; one panel
 
 
+# ---------------------------------------------------------------- maps smaller than the kernel and the tile ----
+# The tg_* shapes: maps of a few pixels — the last layers of a network on a small input — through every conv family (TINY_REACH;
+# tests/test_tiny_cases_cpu.py re-derives it and proves every workgroup a stage, tests/test_gpu_tiny_cases.py runs them on dense sums).
+# Kept out of SHAPES: the probe tests are parametrised over SHAPES and ask that half of a probe's outputs be informative, which a
+# 1 x 1 map under a 3x3 kernel (one live tap of nine) cannot give.  Base quantisation: 32 input channels in four sub-spaces of 8 dims,
+# K = 128, one group, 128 channels — the tile, 16-wave symmetric, eight-wave and half-panel families are all eligible.
+def _tg(H, W, knl, stride, pad, Cin=32, Ct=128, grp=1, M=4, K=128, Cs=8):
+    return ("conv", conv_geom(H, W, Cin, knl, stride, pad, grp, Ct), M, K, Cs, None)
+
+
+TINY_BASE = {
+    "tg_1x1": _tg(1, 1, 3, 1, 1),        # one live tap of nine; every tile larger than the map in both axes
+    "tg_row": _tg(1, 4, 3, 1, 1),        # Ho = 1
+    "tg_col": _tg(7, 1, 3, 1, 1),        # Wo = 1; the three sliding forms (two segments), their column strip wider than the map
+    "tg_k5": _tg(2, 3, 5, 1, 2),         # kernel larger than the map in both axes: every window clipped on both sides
+    "tg_pad2": _tg(2, 2, 3, 1, 2),       # pad = knl - 1, the largest admitted: 4 x 4 outputs, the corner windows hold one pixel
+    "tg_s2": _tg(3, 4, 5, 2, 2),         # stride 2, clipped at both ends: 2 x 2 outputs
+    "tg_fit": _tg(3, 3, 3, 1, 0),        # map = kernel, unpadded: one output
+    "tg_gap": _tg(7, 8, 2, 3, 0),        # stride > knl: source rows and columns inside a tile's receptive field that no window holds
+    "tg_s4": _tg(4, 9, 3, 4, 1),         # stride > knl with padding: 1 x 3 outputs
+    "tg_1x2": _tg(1, 2, 3, 1, 1),        # 8 stages per tile: the split eight-wave form cuts it into slices of one and two stages
+}
+TINY_SHAPES = dict(TINY_BASE)
+# every row with 512 channels: two eight-wave chunks of 1x3 tiles, 1x1 tiles of the 16-wave kernel, half panels of 64 channels per wave
+TINY_SHAPES.update({n + "_c512": (k, dict(g, Ct=512), M, K, Cs, mr) for n, (k, g, M, K, Cs, mr) in TINY_BASE.items()})
+TINY_SHAPES.update({
+    "tg_1x1_c192": _tg(1, 1, 3, 1, 1, Ct=192),                        # 24 / 48 channels per wave, 2x2 / 2x4 tiles on one pixel
+    "tg_1x1_c384": _tg(1, 1, 3, 1, 1, Ct=384),                        # 48 channels per wave, 1x2 / 2x2 tiles
+    "tg_k5_g2": _tg(2, 3, 5, 1, 2, Cin=40, Ct=256, grp=2, M=3),       # 8 + 8 + 4 dims per group: the ragged sub-space's over-read on a two-row map
+    "tg_pad2_m7": _tg(2, 2, 3, 1, 2, Cin=28, M=7, K=32, Cs=4),        # stages of G = 4 sub-spaces, the last of every pixel holds 3
+    # one 3-dim sub-space: the decoded panel form (clamped instantiations) and the few-image kernel, as the dp_* shapes
+    "tg_1x1_d": _tg(1, 1, 3, 1, 1, Cin=3, Ct=64, M=1, Cs=4),
+    "tg_k5_d": _tg(2, 3, 5, 1, 2, Cin=3, Ct=96, M=1, Cs=4),
+    "tg_pad2_d": _tg(2, 2, 3, 1, 2, Cin=3, Ct=64, M=1, Cs=8),
+})
+TINY_DEC = sorted(n for n in TINY_SHAPES if n.endswith("_d"))
+TINY_TABLE = sorted(n for n in TINY_SHAPES if not n.endswith("_d"))
+# the same geometries for the precise path (k_dense) — and the one at which its upper tap bound used to leave the map:
+# H = 1, 3x3 / 2, pad 1: (pad - kh + H - 1) / stride = -1 / 2 truncates to 0 for kh = 2 (qcnn_dense.hip)
+TINY_DENSE = dict({n: TINY_BASE[n][1] for n in TINY_BASE}, tg_1x1_s2=conv_geom(1, 1, 32, 3, 2, 1, 1, 128))
+
+# What the planner and the launchers choose for each tg_* shape, in the layout of PANEL_REACH (stage, live families with channels
+# per wave, tile / strip, chunks, tiles per axis / strips, stages of the heaviest tile; split forms (Z, first split rank) at ONE
+# panel; dead = not eligible, cost 0) plus small = the few-image launcher's (TH, TW, MC, CH, channel chunks per group, G) as
+# SMALL_REACH and, for the tg_*_d shapes, dec = the decoded panel form's (S, NS, T, instantiation at > 16 images, at <= 16, channel
+# chunks) as DEC_REACH.  A sliding form needs Ho >= 2 x slots output rows: of these maps only tg_col's 7 rows have them, everything
+# else falls back to the tile form of its family.  A split form is listed where the planner cuts at one panel (Z > 1).
+TINY_REACH = {
+    "tg_1x1": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (1, 1), 4), "sym16": (8, 2, 2, 1, (1, 1), 4), "sym8": (16, 2, 3, 1, (1, 1), 4),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 4)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(1, 1, 4, 128, 1, 1)),
+    "tg_row": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (1, 2), 16), "sym16": (8, 2, 2, 1, (1, 2), 12), "sym8": (16, 2, 3, 1, (1, 2), 16),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 16), "split_sym8": (5, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(1, 2, 4, 128, 1, 1)),
+    "tg_col": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (7, 1), 12), "slide16": (12, 3, 1, 1, 1, 28), "sym16": (8, 2, 2, 1, (4, 1), 16),
+              "sym8": (16, 2, 3, 1, (4, 1), 16), "sym8_slide": (16, 3, 2, 1, 1, 28), "half8": (32, 3, 4, 2, 1, (3, 1), 20),
+              "half8_slide": (32, 3, 4, 2, 1, 1, 28), "split_sym8": (4, 0)},
+        dead=(), small=(2, 1, 4, 128, 1, 1)),
+    "tg_k5": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (2, 1), 24), "sym16": (8, 2, 2, 1, (1, 2), 24), "sym8": (16, 2, 3, 1, (1, 1), 24),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 24), "split_tile": (4, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 1, 1)),
+    "tg_pad2": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (4, 2), 16), "sym16": (8, 2, 2, 1, (2, 2), 16), "sym8": (16, 2, 3, 1, (2, 2), 16),
+              "half8": (32, 3, 4, 2, 1, (2, 1), 16), "split_sym8": (6, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 1, 1)),
+    "tg_s2": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (2, 1), 48), "sym16": (8, 2, 2, 1, (1, 1), 48), "sym8": (16, 2, 3, 1, (1, 1), 48),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 48), "split_tile": (8, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 1, 1)),
+    "tg_fit": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (1, 1), 36), "sym16": (8, 2, 2, 1, (1, 1), 36), "sym8": (16, 2, 3, 1, (1, 1), 36),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 36), "split_tile": (6, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(1, 1, 4, 128, 1, 1)),
+    "tg_gap": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (2, 1), 64), "sym16": (8, 2, 2, 1, (1, 2), 100), "sym8": (16, 2, 3, 1, (1, 1), 160),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 160), "split_tile": (8, 0), "split_sym8": (2, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 1, 1)),
+    "tg_s4": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (1, 1), 72), "sym16": (8, 2, 2, 1, (1, 2), 48), "sym8": (16, 2, 3, 1, (1, 1), 72),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 72), "split_tile": (8, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(1, 2, 4, 128, 1, 1)),
+    "tg_1x2": dict(
+        stage=(1, 1, 4),
+        live={"tile": (12, 1, 3, 1, (1, 1), 8), "sym16": (8, 2, 2, 1, (1, 1), 8), "sym8": (16, 2, 3, 1, (1, 1), 8),
+              "half8": (32, 3, 4, 2, 1, (1, 1), 8), "split_sym8": (6, 0)},
+        dead=("slide16", "sym8_slide", "half8_slide"), small=(1, 2, 4, 128, 1, 1)),
+    "tg_1x1_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (1, 1), 4), "sym8": (32, 1, 3, 2, (1, 1), 4), "half8": (64, 1, 3, 1, 1, (1, 1), 4)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(1, 1, 4, 128, 4, 1)),
+    "tg_row_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (1, 4), 12), "sym8": (32, 1, 3, 2, (1, 2), 16), "half8": (64, 1, 3, 1, 1, (1, 2), 16),
+              "split_sym8": (6, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(1, 2, 4, 128, 4, 1)),
+    "tg_col_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (7, 1), 12), "slide16": (12, 3, 1, 4, 1, 28), "sym8": (32, 1, 3, 2, (7, 1), 12),
+              "sym8_slide": (32, 3, 1, 2, 1, 28), "half8": (64, 1, 3, 1, 1, (7, 1), 12), "half8_slide": (64, 3, 1, 1, 1, 1, 28)},
+        dead=("sym16",), small=(2, 1, 4, 128, 4, 1)),
+    "tg_k5_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (2, 3), 24), "sym8": (32, 1, 3, 2, (2, 1), 24), "half8": (64, 1, 3, 1, 1, (2, 1), 24),
+              "split_tile": (4, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 4, 1)),
+    "tg_pad2_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (4, 4), 16), "sym8": (32, 1, 3, 2, (4, 2), 16), "half8": (64, 1, 3, 1, 1, (4, 2), 16),
+              "split_sym8": (3, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 4, 1)),
+    "tg_s2_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (2, 2), 48), "sym8": (32, 1, 3, 2, (2, 1), 48), "half8": (64, 1, 3, 1, 1, (2, 1), 48),
+              "split_tile": (6, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 4, 1)),
+    "tg_fit_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (1, 1), 36), "sym8": (32, 1, 3, 2, (1, 1), 36), "half8": (64, 1, 3, 1, 1, (1, 1), 36),
+              "split_tile": (6, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(1, 1, 4, 128, 4, 1)),
+    "tg_gap_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (2, 3), 16), "sym8": (32, 1, 3, 2, (2, 1), 64), "half8": (64, 1, 3, 1, 1, (2, 1), 64),
+              "split_tile": (2, 0), "split_sym8": (2, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(2, 2, 4, 128, 4, 1)),
+    "tg_s4_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (1, 3), 24), "sym8": (32, 1, 3, 2, (1, 1), 72), "half8": (64, 1, 3, 1, 1, (1, 1), 72),
+              "split_tile": (2, 0), "split_sym8": (6, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(1, 2, 4, 128, 4, 1)),
+    "tg_1x2_c512": dict(
+        stage=(1, 1, 4),
+        live={"tile": (24, 1, 1, 2, (1, 2), 8), "sym8": (32, 1, 3, 2, (1, 1), 8), "half8": (64, 1, 3, 1, 1, (1, 1), 8),
+              "split_sym8": (4, 0)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(1, 2, 4, 128, 4, 1)),
+    "tg_1x1_c192": dict(
+        stage=(1, 1, 4),
+        live={"tile": (16, 1, 2, 1, (1, 1), 4), "sym8": (24, 2, 2, 1, (1, 1), 4), "half8": (48, 2, 4, 2, 1, (1, 1), 4)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(1, 1, 4, 128, 2, 1)),
+    "tg_1x1_c384": dict(
+        stage=(1, 1, 4),
+        live={"tile": (32, 1, 1, 1, (1, 1), 4), "sym8": (48, 1, 2, 1, (1, 1), 4), "half8": (48, 2, 2, 1, 1, (1, 1), 4)},
+        dead=("slide16", "sym16", "sym8_slide", "half8_slide"), small=(1, 1, 4, 128, 3, 1)),
+    "tg_k5_g2": dict(
+        stage=(1, 1, 3),
+        live={"tile": (12, 1, 3, 1, (2, 1), 18), "split_tile": (3, 0)},
+        dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(2, 2, 3, 128, 1, 1)),
+    "tg_pad2_m7": dict(
+        stage=(4, 3, 2),
+        live={"tile": (12, 1, 3, 1, (4, 2), 8)},
+        dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(2, 2, 7, 128, 1, 4)),
+    "tg_1x1_d": dict(
+        stage=(1, 1, 1),
+        live={"tile": (6, 2, 3, 1, (1, 1), 1)},
+        dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(1, 1, 1, 64, 1, 1), dec=(80, 3, 9, (4, 1, True, 2, 4), (2, 4, True, 2, 1), 1)),
+    "tg_k5_d": dict(
+        stage=(1, 1, 1),
+        live={"tile": (8, 2, 2, 1, (1, 2), 6)},
+        dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(2, 2, 1, 96, 1, 1), dec=(112, 4, 20, (2, 1, True, 3, 4), (2, 4, True, 2, 1), 3)),
+    "tg_pad2_d": dict(
+        stage=(1, 1, 1),
+        live={"tile": (6, 2, 3, 1, (2, 2), 4)},
+        dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(2, 2, 1, 64, 1, 1), dec=(80, 3, 9, (4, 1, True, 2, 4), (2, 4, True, 2, 1), 1)),
+}
+
+
 def dec_dense_rel(kind, g, split_bf16=False):
     """Relative bound of one output of a decoded layer with ordinary parameters, per unit of mag = |bias| + sum |x_j c_j|, valid for
     ANY summation order.  f32 (conv, both forms; FC with any slice count): the output is bias plus n = Cin knl^2 (FC: D) products

@@ -19,7 +19,9 @@ The clean value: on the integer data of tests/exact_cases.py the integer sum its
 engine's clean run, which is additionally held per element to the float64 sum of table_probe.dense_expected (bound as in
 tests/test_gpu_panel_cases.py; fp16-rounded entries add 2^-11 of mag and 2^-25 per subnormal entry), so a wrong clean run cannot
 vouch for itself.  The few-image kernels run three images: one clean, one with one poisoned element, one all NaN.  An FC output
-depends on every input dim of its image, so FC cases have image and stale isolation only."""
+depends on every input dim of its image, so FC cases have image and stale isolation only.  The ten base rows of
+table_probe.TINY_SHAPES — maps of a few pixels, where nearly every tap is a clipping select — run the same poisoned and stale runs
+through every family table_probe.TINY_REACH lists and through the few-image kernel."""
 import numpy as np
 import pytest
 
@@ -99,7 +101,9 @@ def runner(eng, kind, via, out_layer=1):
         if via == "layer":
             y = eng.run_layer(0, x, n)
         else:
-            inp = np.ascontiguousarray(x.transpose(0, 3, 1, 2)) if kind == "conv" else x.reshape(n, -1, 1, 1).copy()
+            # a copy in either case: scrub() below zeroes it, and np.ascontiguousarray returns a VIEW of x for a 1 x 1 map (the
+            # transposed axes have length 1), which would zero the caller's clean images
+            inp = x.transpose(0, 3, 1, 2).copy() if kind == "conv" else x.reshape(n, -1, 1, 1).copy()
             prob, top5 = eng.forward_host(inp)
             scrub(inp, prob)
             y = eng.layer_output(out_layer, n)
@@ -191,6 +195,8 @@ def conv_families(name):
     kind, g, M, K, Cs = ic.shape_of(name)
     if name in ic.IG:
         return [EXACT, TILE] + [FAMS[k] for k in ORDER if k in ic.IG_REACH[name]["live"]]
+    if name in ic.TG:                                    # maps of a few pixels: every family table_probe.TINY_REACH lists
+        return [EXACT, TILE] + [FAMS[k] for k in ORDER if k in tp.TINY_REACH[name]["live"]]
     if pseudo(K) > 1:                                    # K > 128: the exact-builder kernel under every option
         return [EXACT, dict(TILE, exact=True)]
     f16 = [] if name not in ec.CONV else F16_CONV if ec.EXACT_REACH[name] is not None else F16_APRX
@@ -210,7 +216,7 @@ def conv_data(name, relu=True):
     return kind, g, M, K, Cs, all_params(kind, g, p0, relu), x, None, want64, mag
 
 
-@pytest.mark.parametrize("name", sorted(tp.PANEL_REACH) + ic.IG)
+@pytest.mark.parametrize("name", sorted(tp.PANEL_REACH) + ic.IG + ic.TG)
 def test_conv_panel_families(name):
     kind, g, M, K, Cs, allp, x, exact_want, want64, mag = conv_data(name)
     for f in conv_families(name):
@@ -267,7 +273,7 @@ def few_case(name, f, kind, g, M, K, Cs, allp, x, want64, mag):
     print("%s: code %r, %d poisons, (hit, un-hit) outputs of image 1: %r; stale run clean" % (what, code, len(rows), rows))
 
 
-@pytest.mark.parametrize("name", sorted(n for n in tp.SMALL_REACH if tp.SHAPES[n][0] == "conv") + ic.IG)
+@pytest.mark.parametrize("name", sorted(n for n in tp.SMALL_REACH if tp.SHAPES[n][0] == "conv") + ic.IG + ic.TG)
 def test_few_image_conv(name):
     kind, g, M, K, Cs = ic.shape_of(name)
     p0 = layer_params(name, 71)

@@ -8,7 +8,9 @@
     of a ragged sub-space's code words are ignored by the restatement (NaN there changes nothing).
   * Every single-element poison bites on both sides: it reaches at least one output of its image and leaves at least one
     untouched.  The exceptions are the stated ones: FC layers (the whole image), sm_ct24's last pixel (no window covers it), the
-    centre of sm_15_* (all 36 windows); the positions a corner / the centre reaches are the recorded ones.
+    centre of sm_15_* (all 36 windows), and the tg_* maps of a few pixels, where the count of pixels that reach no output and of
+    pixels that reach every output is stated per shape (isolation_cases.TG_PIXELS); the positions a corner / the centre reaches are
+    the recorded ones.
   * Family reach of the new shapes, re-derived from the CPU planner library and the launch rules restated in
     test_panel_cases_cpu.py / test_small_cases_cpu.py / test_exact_cases_cpu.py; k_fc_sym8 refuses a ragged layer by its shape rule.
   * The C oracle on ragged FC layers: it gives the float64 sum within the dense bound (recorded: it does not refuse them)."""
@@ -33,7 +35,7 @@ from test_table_probe_cpu import oracle_out
 
 synth = pkg("synth")
 
-CONV_PANEL = sorted(tp.PANEL_REACH) + ic.IG
+CONV_PANEL = sorted(tp.PANEL_REACH) + ic.IG + ic.TG
 CONV_FEW = sorted(n for n in tp.SMALL_REACH if tp.SHAPES[n][0] == "conv")
 FC_ALL = sorted(ic.ec.FC) + ic.FR + sorted(n for n in tp.SMALL_REACH if tp.SHAPES[n][0] == "fc") + tp.DEC_FC_SHAPES
 EVERY = CONV_PANEL + ["rgb7"] + CONV_FEW + FC_ALL
@@ -117,7 +119,7 @@ def test_hit_is_where_the_float64_sum_is_nan(name):
         for i in range(0, len(p["single"]), n - 1):
             chunk = [(j,) + e[1:] for j, e in enumerate(p["single"][i:i + n - 1])]
             masks.append(ic.mask_of(kind, g, n, chunk, whole=[n - 1]))
-    if few or name in ic.FR or name in ic.IG:
+    if few or name in ic.FR or name in ic.IG or name in ic.TG:
         for _, e in ic.few_plans(kind, g, M, Cs):
             masks.append(ic.mask_of(kind, g, 3, [(1,) + e], whole=[2]))
     for mask in masks:
@@ -180,6 +182,14 @@ def test_every_single_poison_reaches_something_and_not_everything(name):
         assert {(0, 0), (g["H"] - 1, g["W"] - 1)} <= px
         assert {e[3] for e in p["single"]} >= set(ic.channels(kind, g, M, Cs))           # every listed channel is used
         assert any(i < 64 for i, *_ in p["single"]) and any(64 <= i < 126 for i, *_ in p["single"])   # both halves of the panel
+    if name in ic.TG:                                    # stated per shape: how many pixels reach no output, how many every output
+        by_px = {(e[1], e[2]): (not hi.any(), bool(hi.all())) for e, hi in hs}
+        assert all((not hi.any(), bool(hi.all())) == by_px[e[1], e[2]] for e, hi in hs)          # the channel makes no difference
+        got = (sum(v[0] for v in by_px.values()), sum(v[1] for v in by_px.values()), len(by_px))
+        assert got == ic.TG_PIXELS[name] and got[2] == g["H"] * g["W"], (name, got)
+        whole = ic.hit(kind, g, mask)                    # ... and the plan as a whole has NaN and clean outputs side by side
+        assert whole.any() and not whole.all() and whole[p["whole"]].all() and not whole[p["clean"]].any()
+        hs = []
     for e, hi in hs:
         none, every = not hi.any(), hi.all()
         last_pixel = (e[1], e[2]) == (g["H"] - 1, g["W"] - 1)
