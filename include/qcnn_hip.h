@@ -51,6 +51,18 @@
  *   qcnn_get_layer_ms           swIndvLayerLst / DispElpsTime              src/CaffeEva.cc:297-326
  *   qcnn_group_*                the image loop of ExecForwardPass(void)    src/CaffeEva.cc:151-211
  *                               spread over the GPUs of one node (the reference has one loop on one core)
+ *
+ * Map sizes — limits the CALLER has to keep; the library does not refuse what exceeds the first two.  A feature map lives on the
+ * device as panels of H*W*C rows of 128 images, 512 bytes a row.
+ *   - The INPUT map of a quantised conv layer must hold fewer than 2^23 rows (H*W*C < 8388608: 4 GiB per panel).  The conv table
+ *     kernels form the byte offset of a source pixel in 32 bits; beyond that size the offset wraps inside the panel and the bottom
+ *     output rows are built from the top source rows — no error, no NaN, a wrong map.  Output maps, dense (precise-path) layers
+ *     and the ReLU / LRN / pool layers have no such limit.
+ *   - A quantised FC layer must have fewer than 2^23 input dims (32-bit byte offsets into its input panel); a dense one may have more.
+ *   - A first conv layer whose input panel reaches 2 GiB leaves the decoded kernel for the table kernel by itself (same results;
+ *     qcnn_get_layer_split reports -1 instead of -3).
+ *   - A first layer reads the NCHW batch in place only while n*C*H*W*4 < 2^32 bytes per forward; a larger batch is packed first.
+ * The 8-bit input entry points state their own 2 GiB limits below.
  */
 #ifndef QCNN_HIP_H_
 #define QCNN_HIP_H_

@@ -746,6 +746,110 @@ TINY_REACH = {
 }
 
 
+# ---------------------------------------------------------------- maps beyond 2^31 and 2^32 bytes per panel ----
+# The lg_* shapes: the large end of the geometry range (tests/test_large_cases_cpu.py does the offset arithmetic and the teeth,
+# tests/test_gpu_large_cases.py runs them at THREE images: a panel row is 128 lanes whatever the batch, so the byte offsets inside
+# a panel are the large ones while the host arrays stay near 100 MB).  Kept out of SHAPES, as the tg_* shapes are.
+LARGE_SHAPES = {
+    # input panel 127 x 128 x 512 rows of 512 bytes = 4 261 412 864 bytes: source offsets all through [2^31, 2^32), none beyond
+    "lg_in_lo": ("conv", conv_geom(127, 128, 512, 3, 1, 1, 1, 128), 64, 128, 8, None),
+    # 132 x 128 x 512 rows = 4 429 185 024 bytes: source rows 128 .. 131 start beyond 2^32
+    "lg_in_hi": ("conv", conv_geom(132, 128, 512, 3, 1, 1, 1, 128), 64, 128, 8, None),
+    # ... in two groups of 256 channels: the second group's channel offset on top of a pixel offset beyond 2^32
+    "lg_in_hi_g2": ("conv", conv_geom(132, 128, 512, 3, 1, 1, 2, 128), 32, 128, 8, None),
+    # a small input, an output panel of 66 x 64 x 2048 rows = 4 429 185 024 bytes: conv stores, k_conv_sum, ReLU and unpack beyond 2^32
+    "lg_out": ("conv", conv_geom(66, 64, 32, 3, 1, 1, 1, 2048), 4, 128, 8, None),
+    # either side of the decoded panel form's 2^31-byte guard: 1182^2 x 3 rows = 2 145 982 464 bytes, 1183^2 x 3 = 2 149 615 104
+    "lg_dec_lo": ("conv", conv_geom(1182, 1182, 3, 7, 8, 0, 1, 64), 1, 128, 4, None),
+    "lg_dec_hi": ("conv", conv_geom(1183, 1183, 3, 7, 8, 0, 1, 64), 1, 128, 4, None),
+}
+LARGE_BATCH = 3
+LARGE_GLUE_MAP = (132, 128, 512)       # H, W, C of the map the glue kernels (LRN, pool, fused LRN + pool) run on: 4 429 185 024 bytes
+# the shapes whose source-pixel byte offsets pass 2^32: the conv table kernels form them in 32 bits (pixel_off, qcnn_dev.h) and read
+# the top rows instead — held on the CPU tier only (offsets, reach, teeth); the GPU tier runs them through the kernels that do not
+# form that offset (few-image, dense)
+LARGE_WRAPPING = ("lg_in_hi", "lg_in_hi_g2")
+
+
+def panel_bytes(H, W, C):
+    """Bytes of one panel of an H x W x C map: a row of the 128 images of one (pixel, channel) is 512 bytes."""
+    return H * W * C * 512
+
+
+# What the planner and the launchers choose for each lg_* shape, in the layout of TINY_REACH (split forms at ONE panel — the three
+# images of the GPU tier — listed only where the planner cuts there).  Over lg_in_hi and lg_in_hi_g2 every family that forms a
+# source pixel's byte offset (pixel_off, qcnn_dev.h) is live: tile, slide16, sym16, sym8, sym8_slide, half8, half8_slide and the
+# exact builder (the tile kernel under QCNN_LUT_EXACT).
+LARGE_REACH = {
+    # 64 stages per pixel; every family.  The planner cuts nothing at one panel: 5000 tiles and more fill the chip whole
+    "lg_in_lo": dict(
+        stage=(1, 1, 64),
+        live={"tile": (12, 1, 3, 1, (127, 43), 960), "slide16": (12, 3, 1, 1, 128, 24384), "sym16": (8, 2, 2, 1, (64, 64), 1024),
+              "sym8": (16, 2, 3, 1, (64, 43), 1280), "sym8_slide": (16, 3, 2, 1, 64, 32512), "half8": (32, 3, 4, 2, 1, (43, 32), 1920),
+              "half8_slide": (32, 3, 4, 2, 1, 32, 48768)},
+        dead=(), small=(2, 2, 16, 128, 1, 1)),
+    "lg_in_hi": dict(
+        stage=(1, 1, 64),
+        live={"tile": (12, 1, 3, 1, (132, 43), 960), "slide16": (12, 3, 1, 1, 128, 25344), "sym16": (8, 2, 2, 1, (66, 64), 1024),
+              "sym8": (16, 2, 3, 1, (66, 43), 1280), "sym8_slide": (16, 3, 2, 1, 64, 33792), "half8": (32, 3, 4, 2, 1, (44, 32), 1920),
+              "half8_slide": (32, 3, 4, 2, 1, 32, 50688)},
+        dead=(), small=(2, 2, 16, 128, 1, 1)),
+    # 64 channels per group: the 16-wave tile and sliding kernels only (the eight-wave forms start at 65 channels per chunk)
+    "lg_in_hi_g2": dict(
+        stage=(1, 1, 32),
+        live={"tile": (6, 2, 3, 1, (66, 43), 640), "slide16": (6, 3, 2, 1, 64, 16896)},
+        dead=("sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(2, 2, 17, 64, 1, 1)),
+    # 2048 channels: 342 per chunk of the eight-wave tile form, which has no 48-channel split of 2048 — its sliding form does
+    "lg_out": dict(
+        stage=(1, 1, 4),
+        live={"tile": (32, 1, 1, 6, (66, 64), 36), "slide16": (12, 3, 1, 15, 64, 792), "sym8_slide": (32, 3, 1, 8, 64, 792),
+              "half8": (64, 1, 3, 1, 4, (66, 22), 60), "half8_slide": (64, 3, 1, 1, 4, 64, 792)},
+        dead=("sym16", "sym8"), small=(2, 2, 4, 128, 16, 1)),
+    "lg_dec_lo": dict(
+        stage=(1, 1, 1), live={"tile": (6, 2, 3, 1, (74, 49), 345)},
+        dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(2, 2, 1, 64, 1, 1),
+        dec=(80, 6, 42, (4, 1, False, 3, 4), (4, 4, False, 3, 1), 1)),
+    "lg_dec_hi": dict(
+        stage=(1, 1, 1), live={"tile": (6, 2, 3, 1, (74, 50), 345)},
+        dead=("slide16", "sym16", "sym8", "sym8_slide", "half8", "half8_slide"), small=(2, 2, 1, 64, 1, 1),
+        dec=(80, 6, 42, (4, 1, False, 3, 4), (4, 4, False, 3, 1), 1)),
+}
+
+
+def dense_expected_by_taps(g, x, params, rows=None):
+    """dense_expected for a conv layer with any number of sub-spaces and groups, as knl^2 float64 matrix products per group over the
+    decoded weights, summed tap by tap (the multi-sub-space, grouped sibling of dense_expected_one_subspace): for maps too large for
+    dense_expected's gathers.  Every product of two float32 values is exact in float64; only the summation order differs from
+    dense_expected (tests/test_large_cases_cpu.py holds the two together).  rows = (lo, hi): output rows lo .. hi - 1 only."""
+    x = np.asarray(x, np.float32)
+    n, H, W, Cin = x.shape
+    knl, s, pad, grp, Ct = g["knl"], g["stride"], g["pad"], g["grp"], g["Ct"]
+    ctrd = np.asarray(params["ctrd"], np.float32)
+    M, K, Cs = ctrd.shape
+    Ho, Wo = out_hw(g)
+    lo, hi = (0, Ho) if rows is None else rows
+    Cg, Ctg = Cin // grp, Ct // grp
+    a = np.asarray(params["asmt"]).reshape(Ct, knl, knl, M).astype(np.int64)
+    # decoded weights [Ct, kh, kw, Cg]: sub-space m's code word in dims m Cs .. (zero beyond CsEff, cut at Cg)
+    w = ctrd[np.arange(M)[None, None, None, :], a].reshape(Ct, knl, knl, M * Cs)[..., :Cg].astype(np.float64)
+    bias = np.asarray(params["bias"], np.float32).astype(np.float64)
+    want = np.tile(bias, (n, hi - lo, Wo, 1))
+    mag = np.tile(np.abs(bias), (n, hi - lo, Wo, 1))
+    r0, r1 = lo * s - pad, (hi - 1) * s - pad + knl                                 # source rows [r0, r1) of the padded frame
+    xp = np.zeros((n, r1 - r0, W + 2 * pad, Cin))
+    a0, a1 = max(r0, 0), min(r1, H)
+    xp[:, a0 - r0:a1 - r0, pad:pad + W] = x[:, a0:a1]
+    for gi in range(grp):
+        cts, cin = slice(gi * Ctg, (gi + 1) * Ctg), slice(gi * Cg, (gi + 1) * Cg)
+        for kh in range(knl):
+            for kw in range(knl):
+                sl = xp[:, kh:kh + (hi - lo - 1) * s + 1:s, kw:kw + (Wo - 1) * s + 1:s, cin]
+                wt = w[cts, kh, kw].T
+                want[..., cts] += sl @ wt
+                mag[..., cts] += np.abs(sl) @ np.abs(wt)
+    return want, mag
+
+
 def dec_dense_rel(kind, g, split_bf16=False):
     """Relative bound of one output of a decoded layer with ordinary parameters, per unit of mag = |bias| + sum |x_j c_j|, valid for
     ANY summation order.  f32 (conv, both forms; FC with any slice count): the output is bias plus n = Cin knl^2 (FC: D) products
